@@ -17,7 +17,13 @@ unconverged run is not reported under the converged label.
 N > 1: dfl001 does not shard, so ranks run independent
 replicas; value = all ranks' iterations / max wall time over ranks.
 
-Also reported:
+A plain run does only that: setup, warmup, the K timed solves, the result
+line.  --dump-outputs DIR writes what the last timed solve left for its
+caller (rank 0): DIR/x.npy, y.npy, w.npy, z.npy (the solver()-form primal /
+dual vectors and their slacks, float64) and objective.npy (primal and dual
+objective).  The inputs are the stored netlib file, identical run to run.
+
+With --full, also reported (each leg has its own on/off option):
   roofline      -- the dominant phase of the KKT core (most device time in the
                    timed region), measured live with HIP events on the
                    solver's stream; "phases" lists every phase the same way;
@@ -462,12 +468,29 @@ def end_to_end(p, golden, sync):
             "status": ipo_amd.STATUS_TEXT.get(r["status"], r["status"])}
 
 
+def dump_outputs(dirname, ctx, st):
+    """--dump-outputs: the vectors the last solve on `ctx` left for its caller
+    (solver()'s x, y, w, z) and its objectives, one float64 .npy each."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    x, y, w, z = ctx.solution()
+    arrays = {"x": x, "y": y, "w": w, "z": z, "objective": [st["final_pobj"], st["final_dobj"]]}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5, help="timed steps: complete HSD solves to convergence (117 iterations each on dfl001)")
     ap.add_argument("--warmup", type=int, default=1, help="untimed complete solves before the timed ones")
     ap.add_argument("--problem", default="dfl001")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed solve's x, y, w, z and objectives as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baselines, the instrumented solve "
+                         "(roofline, phases), end_to_end and the intpt / banded / hbm / block-angular legs; the "
+                         "options below select among them and have no effect without --full")
     ap.add_argument("--cpu-iters", type=int, default=8, help="HSD iterations of the CPU oracle sample (0 = skip)")
     ap.add_argument("--no-timing", action="store_true", help="skip the instrumented second solve (no roofline)")
     ap.add_argument("--block-angular", choices=["on", "off"], default="on",
@@ -483,6 +506,7 @@ def main():
     ap.add_argument("--hbm", choices=["on", "off"], default="on",
                     help="also time the HBM-bound vector kernels on BASELINE configs[3] (reported under hbm_roofline)")
     args = ap.parse_args()
+    timing = args.full and not args.no_timing
 
     d = Dist()
     import ipo_amd
@@ -492,7 +516,7 @@ def main():
     # in this process touches the GPU (the reference CPU path
     # timed on the node's own host cores)
     cpu_hsd = cpu_intpt = None
-    if d.rank == 0 and d.world == 1 and args.cpu_iters > 0:
+    if args.full and d.rank == 0 and d.world == 1 and args.cpu_iters > 0:
         try:
             cpu_hsd = cpu_baseline(path, args.cpu_iters)
         except Exception as e:  # noqa: BLE001 -- the GPU number stands on its own
@@ -523,17 +547,19 @@ def main():
     converged = d.min(1.0 if converged else 0.0) > 0.5
     total_iters = d.sum(iters)
     value = total_iters / elapsed if converged else None
+    if args.dump_outputs and d.rank == 0:
+        dump_outputs(args.dump_outputs, ctx, st)
     # one more solve with per-phase HIP events on the solver's stream
     # (the events cost ~10 % of wall time, so they stay out of `value`)
     st_t, elapsed_t = st, elapsed / max(args.steps, 1)
-    if not args.no_timing:
+    if timing:
         (_, st_t, _), elapsed_t = timed_replicas(d, lambda: ctx.run("hsd", timing=True), sync)
 
     # dominant kernel: the phase with the most device time in the timed
     # region (HIP events on the solver's stream); algorithmic work per
     # occurrence from the symbolic plan (DESIGN.md "Kernels")
     roof, phases = None, {}
-    if not args.no_timing and sum(st_t["phase_ms"]) > 0:
+    if timing and sum(st_t["phase_ms"]) > 0:
         for i, name in enumerate(ipo_amd.PHASES):
             ms, nl, cnt = st_t["phase_ms"][i], st_t["phase_launches"][i], st_t["phase_count"][i]
             if nl == 0 or ms <= 0:
@@ -617,7 +643,7 @@ def main():
                    "setup_s": ctx.setup_seconds, "lnz": st["lnz"], "nsup": st["nsup"], "levels": st["nlevels"],
                    "factor_ms_total": st_t["factor_ms"], "solve_ms_total": st_t["solve_ms"],
                    "refine_passes": st["refine_passes"],
-                   "phase_timing": "second identical solve with HIP events" if not args.no_timing else None},
+                   "phase_timing": "second identical solve with HIP events" if timing else None},
         "roofline": roof,
         # the whole IPM iteration against SURVEY.md 8(d)'s algorithmic work
         # (narth + sweeps + SpMVs + vectors), over the timed region
@@ -625,7 +651,7 @@ def main():
                                     per="IPM iteration (SURVEY.md 8(d) algorithmic work), timed region")
                                if iters else None),
         "phases": phases,
-        "mfma_counters": pmc_mfma(),
+        "mfma_counters": pmc_mfma() if args.full else None,
         "cpu_baseline": None,
     }
     if cpu_hsd is not None:
@@ -633,6 +659,11 @@ def main():
         if value is not None and "value" in cpu_hsd:
             out["config"]["speedup_vs_cpu_baseline"] = value / cpu_hsd["value"]
     ctx.close()
+    if not args.full:
+        if d.rank == 0:
+            print(json.dumps(out), flush=True)
+        d.close()
+        return
     if d.rank == 0:
         try:
             out["end_to_end"] = end_to_end(p, golden, sync)

@@ -33,7 +33,8 @@ def pytest_collection_modifyitems(config, items):
             it.add_marker(skip)
 
 
-_MPS_CACHE = os.path.join(os.environ.get("TMPDIR", "/tmp"), "ipo_hip_mps_cache")
+# per user: a cache left behind by another user is not writable
+_MPS_CACHE = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"ipo_hip_mps_cache_{os.getuid()}")
 
 
 def mps_path(name: str) -> str:

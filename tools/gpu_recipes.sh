@@ -23,7 +23,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 STEP="bash tools/gpu_step.sh"
-B1="python3 bench.py --cpu-iters 0 --banded off --block-angular off --hbm off --intpt off"
+B1="python3 bench.py --full --cpu-iters 0 --banded off --block-angular off --hbm off --intpt off"
 PYT="python3 -u -m pytest -x -q --timeout 300 --timeout-method thread"
 
 recipe=$1; shift
