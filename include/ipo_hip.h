@@ -90,8 +90,6 @@ typedef struct {
     double phase_bytes[8];   /* algorithmic bytes of one occurrence                   */
     long   tail_repairs;     /* dense-tail block columns redone after a bail-out      */
     long   tail_dep_rounds;  /* k_tail_dep launches of those repairs                  */
-    long   tail_chain_aborts;/* dense-tail chain launches aborted (a contradicted
-                              * dropped column): factorisation redone per step     */
 } ipo_hip_stats;
 
 /* method: 0 = hsd, 1 = intpt, 2 = hsdls.  trace may be NULL (silent).  timing != 0
@@ -244,14 +242,17 @@ int ipo_hip_synth_block_angular(int nblocks, int mb, int nb, int per_col, int ba
                                 double *b, double *c, double *xs, double *ys, double *ws, double *zs);
 
 /* The persistent dense tail's work-item schedule (host-only; test entry, no
- * reference counterpart): kind 0 k_tail_run's (kkt_dense.hip
- * tail_run_schedule), 1 k_tail_chain_run's, for a tail of nt columns, visit
- * chunks of K blocks, latest chunk L, at most cap workgroups per launch.
+ * reference counterpart): k_tail_run's (kkt_dense.hip tail_run_schedule),
+ * for a tail of nt columns, visit chunks of K blocks, latest chunk L, at most
+ * cap workgroups per launch.  nt may give at most 255 block columns (the
+ * items pack block indices into 8 bits): more is an error.
  * items[2 i], items[2 i + 1] = item i's (x, y) words, ptr[t] = first item of
  * launch t (ntb + 1 entries, ntb = ceil(nt / 64)); either may be NULL.
  * Returns the item count (items are written up to max_items), or -1
- * (ipo_hip_last_error). */
-int ipo_hip_tail_schedule(int kind, int nt, int K, int L, int cap, unsigned *items, int max_items, int *ptr);
+ * (ipo_hip_last_error).  (Until the chain schedule was removed this was
+ * ipo_hip_tail_schedule with a leading `kind` argument; the new name keeps a
+ * caller built for that argument list from binding to this one.) */
+int ipo_hip_tail_run_schedule(int nt, int K, int L, int cap, unsigned *items, int max_items, int *ptr);
 
 int ipo_hip_device_count(void);
 /* hipDeviceSynchronize on the calling thread's device (bench.py brackets its

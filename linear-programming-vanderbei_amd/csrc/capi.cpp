@@ -20,7 +20,6 @@
 namespace ipo {
 // kkt_dense.hip (declared in kkt_kernels.h, which holds device code)
 std::vector<uint2> tail_run_schedule(int ntb, int nt, int K, int L, int cap, std::vector<int>& ptr);
-std::vector<uint2> tail_chain_schedule(int ntb, int nt, int K, int L, int cap, std::vector<int>& ptr);
 }  // namespace ipo
 
 namespace {
@@ -92,7 +91,6 @@ void fill_stats(ipo_hip_stats* st, const ipo::IpmResult& r, const ipo::KktDevice
                          r.kkt.phase_launches[ipo::kPhSyrk];
     st->tail_repairs = r.kkt.tail_repairs;
     st->tail_dep_rounds = r.kkt.tail_dep_rounds;
-    st->tail_chain_aborts = r.kkt.tail_chain_aborts;
     static_assert(ipo::kNumPhases <= 8, "ipo_hip_stats holds 8 phases");
     for (int ph = 0; ph < ipo::kNumPhases; ph++) {
         st->phase_ms[ph] = r.kkt.phase_ms[ph];
@@ -741,14 +739,16 @@ int ipo_hip_vector_bench(int m, int n, const int* kA, const int* iA, const doubl
     }
 }
 
-int ipo_hip_tail_schedule(int kind, int nt, int K, int L, int cap, unsigned* items, int max_items, int* ptr) {
+int ipo_hip_tail_run_schedule(int nt, int K, int L, int cap, unsigned* items, int max_items, int* ptr) {
     try {
-        if (nt <= 0 || K <= 0 || L <= 0 || cap <= 1 || (kind != 0 && kind != 1))
-            throw std::invalid_argument("tail_schedule: bad arguments");
+        if (nt <= 0 || K <= 0 || L <= 0 || cap <= 1) throw std::invalid_argument("tail_schedule: bad arguments");
         const int ntb = (nt + ipo::kPanelCols - 1) / ipo::kPanelCols;
+        // the items pack block indices into 8 bits (the plan constructor's limit)
+        if (ntb > ipo::kTailSchedMaxBlocks)
+            throw std::invalid_argument("tail_schedule: nt gives " + std::to_string(ntb) + " block columns, the limit is " +
+                                        std::to_string(ipo::kTailSchedMaxBlocks));
         std::vector<int> pv;
-        const std::vector<uint2> v = kind == 0 ? ipo::tail_run_schedule(ntb, nt, K, L, cap, pv)
-                                               : ipo::tail_chain_schedule(ntb, nt, K, L, cap, pv);
+        const std::vector<uint2> v = ipo::tail_run_schedule(ntb, nt, K, L, cap, pv);
         const int n = static_cast<int>(v.size());
         if (items)
             for (int i = 0; i < std::min(n, max_items); i++) {

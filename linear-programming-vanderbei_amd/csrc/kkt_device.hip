@@ -3300,7 +3300,6 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
         // 2 every launch of at most kFlatMaxChunks chunks
         int flat_mode = 1;
         if (const char* e = std::getenv("IPO_HIP_GATHER_STAMPS")) gst_group_ = std::atoi(e);
-        if (const char* e = std::getenv("IPO_HIP_GRAPH")) graph_on_ = std::atoi(e) != 0;
         // quadrant gathers (k_update_quad) on the narrow levels of deep trees
         // (IPO_HIP_GATHER_QUAD=0: off)
         bool quad_mode = true;
@@ -3614,7 +3613,7 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
         }
     }
     if (const char* vb = std::getenv("IPO_HIP_VISIT_BLOCKS")) visit_blocks_ = std::max(1, std::atoi(vb));
-    if (plan_.nt > 0 && plan_.ntb <= 255) {
+    if (plan_.nt > 0 && plan_.ntb <= kTailSchedMaxBlocks) {
         // look-ahead launches of at most one workgroup per CU (tail_visit_schedule)
         const char* vs = std::getenv("IPO_HIP_VISIT_SCHED");
         if (!vs || std::atoi(vs) != 0) {
@@ -3637,7 +3636,6 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
             IPO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
             const char* vl = std::getenv("IPO_HIP_VISIT_LATEST");
             const int latest = vl ? std::max(1, std::atoi(vl)) : kTailVisitLatest;
-            run_latest_ = latest;
             const std::vector<uint2> items =
                 tail_run_schedule(plan_.ntb, plan_.nt, visit_blocks_, latest, cus, run_ptr_);
             drun_items_.upload(items, s);
@@ -3654,21 +3652,6 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
                 run_epoch_ = 0;
             }
             IPO_HIP_CHECK(hipStreamSynchronize(s));   // items is a local
-            // the chain launch (IPO_HIP_TAIL_CHAIN=1, where the tail has tiles
-            // below its blocks; used when TailView::dep == 1, else the run above)
-            const char* tc = std::getenv("IPO_HIP_TAIL_CHAIN");
-            tail_chain_ = plan_.ntb >= 3 && tc && std::atoi(tc) != 0;
-            if (tail_chain_) {
-                std::vector<int> cptr;
-                const std::vector<uint2> citems =
-                    tail_chain_schedule(plan_.ntb, plan_.nt, visit_blocks_, latest, cus, cptr);
-                chain_n_ = static_cast<int>(citems.size());
-                dchain_items_.upload(citems, s);
-                dchain_cnt_.alloc(chain_zero_ints(plan_.ntb));
-                dchain_pub_.alloc(static_cast<size_t>(plan_.ntb) * 4 * kChainWinPub);
-                dchain_save_.alloc(2 * kPanelCols * kPanelCols + kPanelCols);
-                IPO_HIP_CHECK(hipStreamSynchronize(s));
-            }
         }
     }
     if (const char* ts = std::getenv("IPO_HIP_TAIL_SPEC")) tail_spec_ = std::atoi(ts);
@@ -3892,7 +3875,6 @@ KktDevice::~KktDevice() {
     if (ev2_) (void)hipEventDestroy(ev2_);
     if (ev3_) (void)hipEventDestroy(ev3_);
     for (hipEvent_t e : kev_) (void)hipEventDestroy(e);
-    if (lvl_exec_) (void)hipGraphExecDestroy(lvl_exec_);
 }
 
 static PlanView make_view(const KktPlan&, const DevBuf<int>& col0, const DevBuf<int>& rowptr, const DevBuf<int>& rows,
@@ -4005,14 +3987,6 @@ void KktDevice::factor_core(const double* dE, const double* dD) {
     const char* rp = std::getenv("IPO_HIP_TAIL_REPAIR");
     const bool repair = use_panel_ && !xch_ && (!rp || std::atoi(rp) != 0);
     bool ok = factor_pass(dE, dD, use_panel_, use_panel_);
-    if (!ok && (hFlags_[1] & 64)) {
-        // the chain launch aborted (a tile contradicted a dropped column): the
-        // factorisation again with the per-step look-ahead and its repairs
-        tm_.tail_chain_aborts++;
-        chain_off_ = true;
-        ok = factor_pass(dE, dD, use_panel_, use_panel_);
-        chain_off_ = false;
-    }
     if (!ok) {
         tm_.panel_redos++;
         for (int b = 0; b < 4; b++) tm_.redo_where[b] += (hFlags_[1] >> b) & 1;
@@ -4060,35 +4034,12 @@ bool KktDevice::factor_pass(const double* dE, const double* dD, bool fused, bool
                        dFlags_.get(), dkQ_.get() ? dQdiag_.get() : static_cast<const double*>(nullptr),
                        static_cast<double>(qmax_));
     const TailView tv = tail_view();
-    // the sparse levels and the dense tail's gather: the same launches every
-    // factorisation of a plan (fixed arguments), so the fused form can be
-    // captured once as a HIP graph and replayed (IPO_HIP_GRAPH=1, opt-in;
-    // per-phase timing and the gather stamps launch them one by one).
-    // Measured: dfl001 unchanged (292.9 / 292.8 against 293.7 / 291.5 it/s),
-    // 25fv47 by intpt +1-3 %; the launches' cost is on the device (~4.5 us
-    // per dispatch), not the host's enqueue, and rocprofv3 --kernel-trace
-    // --stats crashed in the runtime on the replayed graph, so off
-    if (graph_on_ && fused && !timing_ && gst_group_ < 0 && !xch_) {
-        if (!lvl_exec_) {
-            hipGraph_t g = nullptr;
-            IPO_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            enqueue_levels(pv, tv, fused, s);
-            IPO_HIP_CHECK(hipStreamEndCapture(s, &g));
-            const hipError_t e = hipGraphInstantiate(&lvl_exec_, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            IPO_HIP_CHECK(e);
-        }
-        IPO_HIP_CHECK(hipGraphLaunch(lvl_exec_, s));
-    } else {
-        enqueue_levels(pv, tv, fused, s);
-    }
+    enqueue_levels(pv, tv, fused, s);
     if (plan_.nt > 0) {
         // shards: S = sum of every shard's assembled + gathered tail (exchange.h)
         xsum(tv.S, static_cast<size_t>(plan_.nt) * plan_.nt, RedOp::Sum);
         xsum(dDscale_.get() + plan_.tail_c0, plan_.nt, RedOp::Sum);
-        if (tail_fused && tail_chain_ && !chain_off_ && tv.dep == 1) {   // kkt_dense.hip, k_tail_chain_run
-            launch_tail_chain_run();
-        } else if (tail_fused && tail_run_) {     // one persistent launch (kkt_dense.hip, k_tail_run)
+        if (tail_fused && tail_run_) {     // one persistent launch (kkt_dense.hip, k_tail_run)
             launch_tail_from(0, true);
         } else if (tail_fused) {     // look-ahead steps (kkt_dense.hip, k_tail_pr)
             // one event pair around the steps (a pair per launch added its
@@ -4251,30 +4202,6 @@ void KktDevice::launch_tail_from(int t0, bool reset) {
     ph_begin(s);
     launch_tail_run(pv, tail_view(), rc, s);
     ph_end(kPhTail, rc.n > 0, s);
-}
-
-// The dense tail around a chain workgroup (kkt_dense.hip, k_tail_chain_run):
-// every counter zeroed, one launch of the whole schedule.
-void KktDevice::launch_tail_chain_run() {
-    hipStream_t s = stream_;
-    const PlanView pv = IPO_VIEW();
-    IPO_HIP_CHECK(hipMemsetAsync(dchain_cnt_.get(), 0, dchain_cnt_.bytes(), s));
-    const int ntb = plan_.ntb;
-    ChainRun rc;
-    rc.items = dchain_items_.get();
-    rc.n = chain_n_;
-    rc.ticket = dchain_cnt_.get();
-    rc.abort = rc.ticket + 1;
-    rc.pdone = rc.ticket + 2;
-    rc.rdone = rc.pdone + ntb;
-    rc.vseq = rc.rdone + static_cast<size_t>(ntb) * ntb;
-    rc.dwin = rc.vseq + static_cast<size_t>(ntb) * ntb;
-    rc.dpub = dchain_pub_.get();
-    rc.save = dchain_save_.get();
-    rc.latest = run_latest_;
-    ph_begin(s);
-    launch_tail_chain(pv, tail_view(), rc, s);
-    ph_end(kPhTail, 1, s);
 }
 
 // The look-ahead dense tail bailed at block column tb (a pivot failed the

@@ -84,16 +84,6 @@ def test_sync_free_sweeps_bitwise():
     assert texts[0] == texts[1]
 
 
-@pytest.mark.parametrize("name,method", [("dfl001", "hsd"), ("25fv47", "intpt"), ("greenbea", "hsd")])
-def test_level_graph_bitwise(name, method):
-    """The sparse levels and the tail gather replayed as one captured HIP
-    graph (IPO_HIP_GRAPH=1, opt-in) against the same launches issued one by
-    one (default): the same kernels with the same arguments in the same
-    order, so the traces are identical."""
-    texts = [_with_env("IPO_HIP_GRAPH", v, lambda: ipo_amd.run_mps(mps_path(name), method))[1] for v in ("0", "1")]
-    assert texts[0] == texts[1]
-
-
 def test_tail_repair():
     """A dependent pivot in the look-ahead dense tail: resuming the look-ahead
     after redoing only the bailed block column (default) and redoing the

@@ -1,9 +1,10 @@
-"""The persistent dense tail's work-item schedules (kkt_dense.hip
-tail_run_schedule / tail_chain_schedule, through ipo_hip_tail_schedule; host
-code, no GPU): every item of the look-ahead factorisation exactly once, and
-every item waiting only on items with smaller tickets -- the property that
-lets k_tail_run / k_tail_chain_run drain on any share of the CUs (DESIGN.md
-section 6.2).  The waits restated from k_tail_run:
+"""The persistent dense tail's work-item schedule (kkt_dense.hip
+tail_run_schedule, through ipo_hip_tail_run_schedule; host code, no GPU): every
+item of the look-ahead factorisation exactly once, and every item waiting
+only on items with smaller tickets -- the property that lets k_tail_run
+drain on any share of the CUs.  The items pack block
+indices into 8 bits, so the entry refuses more than 255 block columns.  The
+waits restated from k_tail_run:
   panel (t, j):  pdone[t - 1] (every panel of step t - 1; with the window
                  hand-off also their published windows), and the visits of
                  its diagonal tile (t, t) and its tile (t + j + 1, t);
@@ -24,17 +25,21 @@ import ipo_amd  # noqa: E402
 PC = 64
 
 
-def schedule(kind, nt, K=6, L=2, cap=256):
-    lib = ipo_amd.lib()
-    f = lib.ipo_hip_tail_schedule
-    f.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.c_int, C.POINTER(C.c_int)]
+def schedule_fn():
+    f = ipo_amd.lib().ipo_hip_tail_run_schedule
+    f.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.c_int, C.POINTER(C.c_int)]
     f.restype = C.c_int
-    n = f(kind, nt, K, L, cap, None, 0, None)
-    assert n > 0, ipo_amd.lib().ipo_hip_last_error
+    return f
+
+
+def schedule(nt, K=6, L=2, cap=256):
+    f = schedule_fn()
+    n = f(nt, K, L, cap, None, 0, None)
+    assert n > 0, ipo_amd.last_error()
     ntb = (nt + PC - 1) // PC
     items = (C.c_uint * (2 * n))()
     ptr = (C.c_int * (ntb + 1))()
-    assert f(kind, nt, K, L, cap, items, n, ptr) == n
+    assert f(nt, K, L, cap, items, n, ptr) == n
     return [(items[2 * i], items[2 * i + 1]) for i in range(n)], list(ptr), ntb
 
 
@@ -72,7 +77,7 @@ def check_visits(vis, panel_idx, ntb, nt):
 @pytest.mark.parametrize("nt,K,L,cap", [(4441, 6, 2, 256), (4441, 6, 6, 256), (4441, 6, 2, 80),
                                         (2000, 6, 2, 256), (732, 6, 2, 256), (155, 6, 2, 256), (640, 4, 1, 32)])
 def test_run_schedule(nt, K, L, cap):
-    items, ptr, ntb = schedule(0, nt, K, L, cap)
+    items, ptr, ntb = schedule(nt, K, L, cap)
     panel_idx, vis = {}, []
     for i, (x, y) in enumerate(items):
         t = y & 0xff
@@ -100,25 +105,13 @@ def test_run_schedule(nt, K, L, cap):
         assert ptr[t] <= i < ptr[t + 1], (i, t)
 
 
-@pytest.mark.parametrize("nt", [4441, 2000, 500])
-def test_chain_schedule(nt):
-    items, ptr, ntb = schedule(1, nt)
-    assert items[0] == (0, 1 << 30)              # the chain item, ticket 0
-    tiles, vis, panel_idx = {}, [], {}
-    for i, (x, y) in enumerate(items[1:], 1):
-        t = y & 0xff
-        if y >> 31:
-            assert (t, x) not in tiles and x >= t + 2
-            tiles[(t, x)] = i
-        else:
-            assert not (y >> 30)
-            vis.append((i, t, x & 255, (x >> 8) & 255, (x >> 16) & 255, x >> 24, (y >> 8) & 0xff))
-    assert sorted(tiles) == sorted((t, R) for t in range(ntb) for R in range(t + 2, ntb))
-    for (t, R), i in tiles.items():
-        if t > 0:
-            assert tiles[(t - 1, R)] < i
-    # the chain factors every panel: its "panels" precede everything
-    for t in range(ntb):
-        for j in range(tail_gp(nt, t)):
-            panel_idx[(t, j)] = 0
-    check_visits(vis, panel_idx, ntb, nt)
+def test_schedule_over_block_limit():
+    """256 block columns (nt = 16321) do not fit the 8-bit item fields: refused, and the error names the limit."""
+    assert schedule_fn()(255 * PC + 1, 6, 2, 256, None, 0, None) == -1
+    err = ipo_amd.last_error()
+    assert "255" in err and "limit" in err, err
+
+
+def test_schedule_at_block_limit():
+    """255 block columns (nt = 16320) are the most the item fields hold: a schedule comes back."""
+    assert schedule_fn()(255 * PC, 6, 2, 256, None, 0, None) > 0

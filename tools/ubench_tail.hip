@@ -65,35 +65,20 @@ int main(int argc, char** argv) {
     // timed as one launch, its pivots and factor compared with the per-step
     // launches' (another grouping of the visits' sums: not bitwise)
     // UB_WINPUB=0: the run without the window hand-off (RunPub)
-    // UB_CHAIN=1: the chain launch (k_tail_chain_run) instead of the run
-    const bool chain = std::getenv("UB_CHAIN") && std::atoi(std::getenv("UB_CHAIN")) != 0;
-    const bool run = chain || (std::getenv("UB_RUN") && std::atoi(std::getenv("UB_RUN")) != 0);
+    const bool run = (std::getenv("UB_RUN") && std::atoi(std::getenv("UB_RUN")) != 0);
     std::vector<int> rptr;
     uint2* ditems = nullptr;
     int* dcnt = nullptr;
-    double *dpub = nullptr, *dsave = nullptr;
-    int ub_latest = 0;
+    const size_t ncnt = 1 + ntb + (size_t)ntb * ntb + ntb;   // ticket, pdone[ntb], vseq[ntb * ntb], pread[ntb]
     int cus_run = 0;
     if (run) {
         CK(hipDeviceGetAttribute(&cus_run, hipDeviceAttributeMultiprocessorCount, 0));
         if (const char* cp = std::getenv("UB_CAP")) cus_run = std::atoi(cp);   // the schedule's items per launch
         const int latest = std::getenv("UB_LATEST") ? std::atoi(std::getenv("UB_LATEST")) : ipo::kTailVisitLatest;
-        const std::vector<uint2> items = chain ? ipo::tail_chain_schedule(ntb, nt, tv.vk, latest, cus_run, rptr)
-                                               : ipo::tail_run_schedule(ntb, nt, tv.vk, latest, cus_run, rptr);
-        if (chain) rptr[ntb] = static_cast<int>(items.size());
-        if (chain && std::getenv("UB_NOVISIT")) {      // timing of the chain and tile items alone (factor wrong)
-            std::vector<uint2> kept;
-            for (const uint2& it : items)
-                if (it.y >> 30) kept.push_back(it);
-            const_cast<std::vector<uint2>&>(items) = kept;
-            rptr[ntb] = static_cast<int>(kept.size());
-        }
-        ub_latest = latest;
+        const std::vector<uint2> items = ipo::tail_run_schedule(ntb, nt, tv.vk, latest, cus_run, rptr);
         CK(hipMalloc(&ditems, items.size() * sizeof(uint2)));
         CK(hipMemcpy(ditems, items.data(), items.size() * sizeof(uint2), hipMemcpyHostToDevice));
-        CK(hipMalloc(&dcnt, ipo::chain_zero_ints(ntb) * sizeof(int)));
-        CK(hipMalloc(&dpub, (size_t)ntb * 4 * ipo::kChainWinPub * sizeof(double)));
-        CK(hipMalloc(&dsave, (2 * 64 * 64 + 64) * sizeof(double)));
+        CK(hipMalloc(&dcnt, ncnt * sizeof(int)));
         std::printf("persistent run: %zu items, latest chunk %d, items per launch", items.size(), latest);
         for (int t = 0; t < ntb; t++) std::printf(" %d", rptr[t + 1] - rptr[t]);
         std::printf("\n");
@@ -102,52 +87,33 @@ int main(int argc, char** argv) {
     // {drawn, ready, done, xcc}, 100 MHz ticks) with each item's record, binary
     unsigned long long* dtrace = nullptr;
     const char* trace_file = std::getenv("UB_TRACE");
-    const size_t trace_n = (size_t)(rptr.empty() ? 0 : rptr[ntb] + ntb) * 4 + (size_t)ntb * 32;
-    if (run && trace_file) CK(hipMalloc(&dtrace, trace_n * sizeof(unsigned long long)));
+    if (run && trace_file) CK(hipMalloc(&dtrace, (size_t)rptr[ntb] * 4 * sizeof(unsigned long long)));
     double* dwpub = nullptr;
     int* dwflag = nullptr;
     int wepoch = 0;
-    if (run && !chain && !(std::getenv("UB_WINPUB") && std::atoi(std::getenv("UB_WINPUB")) == 0)) {
+    if (run && !(std::getenv("UB_WINPUB") && std::atoi(std::getenv("UB_WINPUB")) == 0)) {
         CK(hipMalloc(&dwpub, 2 * (size_t)ntb * 4 * ipo::kTailPubWin * sizeof(double)));
         CK(hipMalloc(&dwflag, (size_t)ntb * ntb * 4 * sizeof(int)));
         CK(hipMemset(dwflag, 0, (size_t)ntb * ntb * 4 * sizeof(int)));
         std::printf("window hand-off on\n");
     }
     auto run_once = [&](hipStream_t st) {
-        CK(hipMemsetAsync(dcnt, 0, ipo::chain_zero_ints(ntb) * sizeof(int), st));
-        if (chain) {
-            ipo::ChainRun rc;
-            rc.items = ditems;
-            rc.n = rptr[ntb];
-            rc.ticket = dcnt;
-            rc.abort = dcnt + 1;
-            rc.pdone = dcnt + 2;
-            rc.rdone = rc.pdone + ntb;
-            rc.vseq = rc.rdone + ntb * ntb;
-            rc.dwin = rc.vseq + ntb * ntb;
-            rc.dpub = dpub;
-            rc.save = dsave;
-            rc.latest = ub_latest;
-            rc.novisit = std::getenv("UB_NOVISIT") ? 1 : 0;
-            rc.trace = dtrace;
-            ipo::launch_tail_chain(pv, tv, rc, st);
-        } else {
-            ipo::TailRun rc;
-            rc.items = ditems;
-            rc.n = rptr[ntb];
-            rc.t0 = 0;
-            rc.ticket = dcnt;
-            rc.pdone = dcnt + 1;
-            rc.vseq = dcnt + 1 + ntb;
-            if (dwpub) {          // the window hand-off (UB_WINPUB=0: off), as the library's default
-                rc.pub = dwpub;
-                rc.wflag = dwflag;
-                rc.pread = dcnt + 1 + ntb + ntb * ntb;
-                rc.epoch = ++wepoch;
-            }
-            rc.trace = dtrace;
-            ipo::launch_tail_run(pv, tv, rc, st);
+        CK(hipMemsetAsync(dcnt, 0, ncnt * sizeof(int), st));
+        ipo::TailRun rc;
+        rc.items = ditems;
+        rc.n = rptr[ntb];
+        rc.t0 = 0;
+        rc.ticket = dcnt;
+        rc.pdone = dcnt + 1;
+        rc.vseq = dcnt + 1 + ntb;
+        if (dwpub) {          // the window hand-off (UB_WINPUB=0: off), as the library's default
+            rc.pub = dwpub;
+            rc.wflag = dwflag;
+            rc.pread = dcnt + 1 + ntb + ntb * ntb;
+            rc.epoch = ++wepoch;
         }
+        rc.trace = dtrace;
+        ipo::launch_tail_run(pv, tv, rc, st);
     };
     std::vector<double> g_step;
     if (run) {      // the per-step launches' pivots and factor, for the comparison
@@ -211,12 +177,12 @@ int main(int argc, char** argv) {
                     same, nt);
         if (dtrace) {
             const size_t ni = rptr[ntb];
-            std::vector<unsigned long long> tr(chain ? trace_n : ni * 4);
+            std::vector<unsigned long long> tr(ni * 4);
             std::vector<uint2> items(ni);
             CK(hipMemcpy(tr.data(), dtrace, tr.size() * 8, hipMemcpyDeviceToHost));
             CK(hipMemcpy(items.data(), ditems, ni * sizeof(uint2), hipMemcpyDeviceToHost));
             FILE* f = std::fopen(trace_file, "wb");
-            const int hdr[2] = {ntb, (int)ni * (chain ? -1 : 1)};
+            const int hdr[2] = {ntb, (int)ni};
             std::fwrite(hdr, 4, 2, f);
             std::fwrite(items.data(), sizeof(uint2), ni, f);
             std::fwrite(tr.data(), 8, tr.size(), f);
