@@ -208,6 +208,13 @@ int ipo_hip_symbolic_q(int m, int n, const int *kA, const int *iA, const int *kQ
  * = strict-lower nonzeros per column of L in the new order. */
 int ipo_hip_symbolic_forced(int m, int n, const int *kA, const int *iA, int nforced, int *perm, int *colcount,
                             long *lnz, int *tail_c0, int *nsup, int *nlevels);
+/* The dense tail of the plan a device factor of this pattern gets (host
+ * only): its first column, its size nt = m + n - tail_c0 (0: no dense tail)
+ * and its 64-column block count.  density <= 0: the density the device
+ * factor itself uses (0.7, or the environment's IPO_HIP_TAIL_DENSITY);
+ * 1: only the reference's full dense window. */
+int ipo_hip_symbolic_tail(int m, int n, const int *kA, const int *iA, double density, int *tail_c0, int *nt,
+                          int *ntb);
 
 /* Synthetic LPs in solver() form (BASELINE configs[3] and configs[4],
  * SURVEY.md §8(d); not part of the reference): feasible and bounded by

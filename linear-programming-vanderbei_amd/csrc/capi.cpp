@@ -691,6 +691,24 @@ int ipo_hip_symbolic_forced(int m, int n, const int* kA, const int* iA, int nfor
     }
 }
 
+int ipo_hip_symbolic_tail(int m, int n, const int* kA, const int* iA, double density, int* tail_c0, int* nt,
+                          int* ntb) {
+    try {
+        std::vector<int> kat, iat;
+        std::vector<double> at, a(kA[n], 1.0);
+        ipo::csc_transpose(m, n, kA, iA, a.data(), kat, iat, at);
+        const double rho = density > 0.0 ? density : ipo::device_tail_density();
+        ipo::KktPlan P = ipo::build_kkt_plan(m, n, kA, iA, kat.data(), iat.data(), 0, rho);
+        if (tail_c0) *tail_c0 = P.tail_c0;
+        if (nt) *nt = P.nt;
+        if (ntb) *ntb = P.ntb;
+        return 0;
+    } catch (const std::exception& e) {
+        set_err(e.what());
+        return -1;
+    }
+}
+
 int ipo_hip_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;

@@ -3103,8 +3103,7 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
     csc_transpose(m, n, kA, iA, A, kat, iat, at);
     // the dense tail reaches down to the longest suffix at least 70 % full
     // (IPO_HIP_TAIL_DENSITY=1: only the reference's full dense window)
-    double tail_density = kTailDensity;
-    if (const char* e = std::getenv("IPO_HIP_TAIL_DENSITY")) tail_density = std::atof(e);
+    const double tail_density = device_tail_density();
     mark("transpose");
     plan_ = build_kkt_plan(m, n, kA, iA, kat.data(), iat.data(), nforced, tail_density, qb ? &qpat : nullptr);
     mark("ordering + symbolic plan");

@@ -214,5 +214,8 @@ struct KktPlan {
 // the reference's dense window)
 KktPlan build_kkt_plan(int m, int n, const int* kA, const int* iA, const int* kAt, const int* iAt,
                        int nforced = 0, double tail_density = 1.0, const QPattern* q = nullptr);
+// The tail density of a device plan (the KktDevice constructor's choice):
+// kTailDensity, overridden by IPO_HIP_TAIL_DENSITY
+double device_tail_density();
 
 }  // namespace ipo

@@ -561,6 +561,11 @@ KktOrdering order_tiered_min_degree(int m, int n, const int* kA, const int* iA,
     return o;
 }
 
+double device_tail_density() {
+    if (const char* e = std::getenv("IPO_HIP_TAIL_DENSITY")) return std::atof(e);
+    return kTailDensity;
+}
+
 KktPlan build_kkt_plan(int m, int n, const int* kA, const int* iA, const int* kAt, const int* iAt, int nforced,
                        double tail_density, const QPattern* q) {
     int leaf = kNdLeafRows;

@@ -80,6 +80,7 @@ EXPORTED = [
     "ipo_hip_set_device", "ipo_hip_rccl_unique_id", "ipo_hip_ctx_create_shard", "ipo_hip_vector_bench",
     "ipo_hip_dot_ordered",
     "ipo_hip_kkt_create_q", "ipo_hip_ldlt_set_q", "ipo_hip_symbolic_q", "ipo_hip_mps_quads",
+    "ipo_hip_symbolic_tail",
 ]
 
 # int (*)(void *user, double *buf, long n, int op)  -- ipo_hip_allreduce_fn
@@ -173,6 +174,8 @@ def lib() -> C.CDLL:
     L.ipo_hip_symbolic_forced.argtypes = [_I, _I, _P, _P, _I, _P, _P, C.POINTER(C.c_long), C.POINTER(_I),
                                           C.POINTER(_I), C.POINTER(_I)]
     L.ipo_hip_symbolic_forced.restype = _I
+    L.ipo_hip_symbolic_tail.argtypes = [_I, _I, _P, _P, _D, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]
+    L.ipo_hip_symbolic_tail.restype = _I
     L.ipo_hip_set_device.argtypes = [_I]
     L.ipo_hip_set_device.restype = _I
     L.ipo_hip_rccl_unique_id.argtypes = [_P]
@@ -570,6 +573,20 @@ def symbolic_forced(m, n, kA, iA, nforced) -> dict:
     if rc:
         raise IpoHipError("symbolic_forced: " + last_error())
     return dict(perm=perm, colcount=cc, lnz=lnz.value, tail_c0=tc.value, nsup=nsup.value, nlevels=nlev.value)
+
+
+def symbolic_tail(m, n, kA, iA, density=None) -> dict:
+    """Host-only: the dense tail of the plan a KktFactor of this pattern gets
+    (tail_c0, nt, ntb).  density None (or <= 0): the device factor's own
+    choice (0.7, or IPO_HIP_TAIL_DENSITY); 1: the reference's dense window."""
+    kA = np.ascontiguousarray(kA, np.int32)
+    iA = np.ascontiguousarray(iA, np.int32)
+    tc, nt, ntb = C.c_int(), C.c_int(), C.c_int()
+    rc = lib().ipo_hip_symbolic_tail(m, n, _ptr(kA), _ptr(iA), 0.0 if density is None else float(density),
+                                     C.byref(tc), C.byref(nt), C.byref(ntb))
+    if rc:
+        raise IpoHipError("symbolic_tail: " + last_error())
+    return dict(tail_c0=tc.value, nt=nt.value, ntb=ntb.value)
 
 
 # ----------------------------------------------------------------- synthetic LPs

@@ -6,7 +6,10 @@ l = a / d, a -= l (l_j d) form, kkt_dense.hip).  On the dense tail the fused
 path defers the trailing update and sums up to four blocks' products in one
 accumulator before subtracting them (visits, kkt_dense.hip), so there the two
 agree to rounding: refined solves to 1e-10 relative, whole IPM solves to the
-HSD parity bar (tests/test_gpu_ipm.py)."""
+HSD parity bar (tests/test_gpu_ipm.py).  Small and edge tails (exact
+multiples of 64 and one row past them, partial last blocks, the whole matrix
+as the tail) and every path here against an extended-precision reference:
+tests/test_gpu_tail_shapes.py."""
 import os
 
 import numpy as np
