@@ -88,8 +88,8 @@ class IpmSolver {
     // (RowAxPlan, row_ax.h; bitwise the residual kernels' own sums), when x is
     // larger than a slice and the solver is not sharded
     void row_ax(const double* x, hipStream_t st);
-    int axblocks_ = 1;
-    bool axsliced_ = false;   // A x by RowAxPlan (x over one L2 slice, or IPO_HIP_AX_JDS=1)
+    const KktKnobs knobs_ = KktKnobs::from_env();   // read once, at construction (kkt_knobs.h)
+    bool axsliced_ = false;   // A x by RowAxPlan (rows_ax_sliced)
     DevBuf<double> ax_;
     RowAxPlan axplan_;
     void print_dims(FILE* tr) const;
@@ -112,7 +112,6 @@ class IpmSolver {
     hipStream_t side_ = nullptr;            // mu / residuals beside the factorisation (run_hsd)
     hipEvent_t ev_step_ = nullptr, ev_side_ = nullptr;
     double* hs_ = nullptr;       // pinned scalars
-    bool full_trace_ = false;    // IPO_HIP_TRACE_FULL: full-precision scalars per iteration on stderr
 };
 
 // Whole-pipeline convenience used by the C ABI: host arrays in, host out.

@@ -345,8 +345,7 @@ IpmSolver::IpmSolver(int m, int n, const int* kA, const int* iA, const double* A
     }
     // LPs with a vector of kOrderedMaxLen entries (none in netlib) take every
     // dot of theirs in the segmented order; IPO_HIP_DOT_SEGMIN overrides
-    dot_segmin_ = std::max(mg_, ng_) >= kOrderedMaxLen ? kSegDotLen : 0;
-    if (const char* e = std::getenv("IPO_HIP_DOT_SEGMIN")) dot_segmin_ = std::max(0, std::atoi(e));
+    dot_segmin_ = knobs_.dot_segmin >= 0 ? knobs_.dot_segmin : std::max(mg_, ng_) >= kOrderedMaxLen ? kSegDotLen : 0;
     if (!stream_) {
         IPO_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
         own_stream_ = true;
@@ -378,11 +377,10 @@ IpmSolver::IpmSolver(int m, int n, const int* kA, const int* iA, const double* A
     IPO_HIP_CHECK(hipEventCreateWithFlags(&ev_step_, hipEventDisableTiming));
     IPO_HIP_CHECK(hipEventCreateWithFlags(&ev_side_, hipEventDisableTiming));
     lax_.alloc(nforced_ > 0 ? nforced_ : 1);
-    axblocks_ = rows_ax_blocks(n_);
-    axsliced_ = rows_ax_sliced(n_) && !xch_;
+    axsliced_ = rows_ax_sliced(knobs_, n_) && !xch_;
     if (axsliced_) {
         ax_.alloc(m_ > 0 ? m_ : 1);
-        axplan_.build(m, n, kA, iA, A, axblocks_, stream_);
+        axplan_.build(m, n, kA, iA, A, knobs_.ax_blocks, stream_);
     }
     IPO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hs_), 16 * sizeof(double), hipHostMallocDefault));
     IPO_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -447,11 +445,9 @@ int IpmSolver::run(const IpmOptions& opt, IpmResult* res) {
 }
 
 int IpmSolver::run_hsd(const IpmOptions& opt, IpmResult* res) {
-    full_trace_ = std::getenv("IPO_HIP_TRACE_FULL") != nullptr;
     // mu, residuals and right-hand sides on a side stream beside the
     // factorisation (one GPU, no exchange); IPO_HIP_OVERLAP=0 turns it off
-    bool overlap = xch_ == nullptr;
-    if (const char* e = std::getenv("IPO_HIP_OVERLAP")) overlap = overlap && std::atoi(e) != 0;
+    const bool overlap = xch_ == nullptr && knobs_.overlap;
     const int m = m_, n = n_;
     hipStream_t s = stream_;
     const int gv = ceil_div(m + n, NT);
@@ -562,7 +558,7 @@ int IpmSolver::run_hsd(const IpmOptions& opt, IpmResult* res) {
         }
         res->final_mu = mu; res->final_pobj = pobj / phi + f_; res->final_dobj = dobj / phi + f_;
         res->final_pinf = normr; res->final_dinf = norms;
-        if (full_trace_) {
+        if (knobs_.trace_full) {
             std::fprintf(stderr, "FT %d %.17g %.17g %.17g %.17g %.17g %.17g\n", iter, pobj, dobj, mu, phi, psi, normr);
             std::fprintf(stderr, "FT   ndep=%d eps=%.1e\n", K.ndep(), K.epsdiag());
         }
@@ -824,8 +820,9 @@ void vector_bench(int m, int n, const int* kA, const int* iA, const double* A, i
     const int gv = static_cast<int>((N + NT - 1) / NT);
     // the residuals as run_hsd forms them: A x column-blocked first when x
     // exceeds one L2 slice (IpmSolver::row_ax), timed together
-    const int axb = rows_ax_blocks(n);
-    const bool sliced = rows_ax_sliced(n);
+    const KktKnobs knobs = KktKnobs::from_env();
+    const int axb = knobs.ax_blocks;
+    const bool sliced = rows_ax_sliced(knobs, n);
     DevBuf<double> axv;
     RowAxPlan axplan;
     if (sliced) { axv.alloc(m > 0 ? m : 1); axplan.build(m, n, kA, iA, A, axb, s); }

@@ -1862,7 +1862,7 @@ int tail_visit_tiles(int ntb, int t, int K) {
 // which are ready from launch b1 on: moved, latest-first, into the latest
 // earlier launch with room.  Every tile keeps its chunks and their order (its
 // first chunk only comes earlier), so the factor is bitwise the same.
-std::vector<unsigned> tail_visit_schedule(int ntb, int nt, int K, int cap, std::vector<int>& ptr) {
+std::vector<unsigned> tail_visit_schedule(int ntb, int nt, int K, int cap, bool xcd, std::vector<int>& ptr) {
     struct V { int bi, c, b0, b1; };
     std::vector<std::vector<V>> L(ntb);
     std::vector<int> tot(ntb, 0);
@@ -1903,9 +1903,9 @@ std::vector<unsigned> tail_visit_schedule(int ntb, int nt, int K, int cap, std::
     // and every visit of column c reads the same blocks L(c, b0 .. b1 - 1)
     // (the B operand, W = L D): the visits of column c go to workgroup ids of
     // one residue mod 8 where possible, so those blocks come from one L2
+    // (xcd; KktKnobs::visit_xcd)
     std::vector<unsigned> out;
     ptr.assign(ntb + 1, 0);
-    const bool xcd = !std::getenv("IPO_HIP_VISIT_XCD") || std::atoi(std::getenv("IPO_HIP_VISIT_XCD")) != 0;
     for (int t = 0; t < ntb; t++) {
         ptr[t] = static_cast<int>(out.size());
         std::vector<V> order;

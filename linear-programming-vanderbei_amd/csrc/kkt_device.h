@@ -16,22 +16,13 @@
 
 #include "hip_util.h"
 #include "exchange.h"
+#include "kkt_knobs.h"
 #include "kkt_plan.h"
 
 namespace ipo {
 
 // Device view of the dense tail (see kkt_plan.h): S = nt x nt column-major.
-// Blocks per visit of the look-ahead dense tail (kkt_dense.hip, visit_hi):
-// IPO_HIP_VISIT_BLOCKS overrides.
-// Measured on dfl001's tail (tools/ubench_tail): per-step launches (round 4)
-// 4 -> 2.43 ms, 6 -> 2.26, 8 -> 2.55; the persistent run with the window
-// hand-off (round 6, latest chunk L in brackets) 3 -> 1.92 (3), 4 -> 1.79
-// (4), 5 -> 1.80 (2-4), 6 -> 1.85 (2), 7 -> 1.96, 8 -> 2.08
-constexpr int kTailVisitBlocks = 4;
-// the persistent tail's latest chunk per column (tail_run_schedule): it must
-// finish within one step (IPO_HIP_VISIT_LATEST overrides); equal to the
-// chunk, every tile receives the per-step launches' chunks (bitwise them)
-constexpr int kTailVisitLatest = 4;
+// (kTailVisitBlocks, kTailVisitLatest: kkt_knobs.h)
 // most block columns of a scheduled tail: the schedules pack block indices
 // and chunk counts into 8 bits each (tail_visit_schedule, tail_run_schedule);
 // a larger tail takes the per-step launches with the visit_hi formula
@@ -164,7 +155,7 @@ class KktDevice {
     void restore_host_state(const HostState& h) { epsdiag_ = h.epsdiag; ndep_ = h.ndep; tm_ = h.tm; }
 
     double epsdiag() const { return epsdiag_; }
-    void set_pivot_tolerance(double t) { pivot_tol_ = t; }
+    void set_pivot_tolerance(double t) { pivot_tol_ = t; }   // (starts at IPO_HIP_PIVTOL, kkt_knobs.h)
     void set_epsdiag(double e) { epsdiag_ = e; }
     // The refinement's residual takes rows row0..m-1 (trailing long rows, an
     // unsharded solve) from one wave each (launch_link_ax: lanes strided,
@@ -185,6 +176,27 @@ class KktDevice {
     double* device_diag() const { return dDg_.get(); }
 
   private:
+    const KktKnobs knobs_ = KktKnobs::from_env();   // every runtime knob, read once (kkt_knobs.h)
+    // the constructor's steps, in order (each returns / takes what crosses steps)
+    void upload_plan(const int* kA, const int* iA, const double* A, const std::vector<int>& kat,
+                     const std::vector<int>& iat, const std::vector<double>& at, const QBlock* qb);
+    void build_panel_units();
+    void build_solve_chunks();
+    void build_sweep_order();
+    // deep trees: the sparse units' k-slots in visit order (build_visit_slots; empty without visits)
+    struct VisitSlots {
+        std::vector<int> kslot, kptr, late_b;     // the slots; per unit: its range's end, its first late slot
+        std::vector<std::vector<int3>> vis;       // per gather group: (unit, slot begin, slot end)
+    };
+    VisitSlots build_visit_slots() const;
+    void build_gather_chunks(const VisitSlots& vs);
+    void count_work();
+    void build_slot_records(const std::vector<int>& kslot_v);
+    void setup_tail(int cus);
+    void alloc_numeric();
+    // the host repair backs the look-ahead panel's dependent pivots (TailView::dep):
+    // not without the fused kernels, not in a sharded solve
+    bool tail_repair() const { return use_panel_ && !xch_ && knobs_.tail_repair; }
     void factor_core(const double* dE, const double* dD);
     void dump_factor(const double* dE, const double* dD, double eps_in);
     int dump_count_ = 0;
@@ -219,7 +231,7 @@ class KktDevice {
     // set (a host emulation of the GPU factor in round 1, tools/tau_sweep.py on the GPU):
     // 2^-46 over-flags twin-column pivots the reference keeps, exact zero
     // under-flags; 1e-17 matched the most hsd and intpt iteration counts.
-    double pivot_tol_ = 1.0e-17;
+    double pivot_tol_ = knobs_.pivtol;
     int last_passes_ = 0;
     bool timing_ = false;
     KktTimers tm_;
@@ -258,7 +270,7 @@ class KktDevice {
     DevBuf<int> dylate_ptr_, dylate_idx_, dpre_col_, dpre_ptr_, dpre_idx_;
     DevBuf<double> dYbuf_;
     // sync-free top levels of the sweeps (k_fwd_sf / k_bwd_sf)
-    void build_sync_free_plan();
+    void build_sync_free_plan(int cus);
     int sf_level_ = 0;                    // first level of the range (nlevels: none)
     int nsf_f_ = 0, nsf_b_ = 0, sf_grid_ = 1;
     int sf_fwd_epoch_ = 0, sf_bwd_epoch_ = 0;
@@ -277,7 +289,7 @@ class KktDevice {
     std::vector<char> split_level_;       // per level: k_diag + k_trsm instead of the fused panels (wide levels)
     std::vector<int> small1_cnt_;         // per level: leading single-column small panels of <= 8 rows (k_panel_s1)
     DevBuf<int> dsmall_sups_;
-    bool use_panel_ = true;               // fused diagonal-block + panel kernels (IPO_HIP_PANEL=0: off)
+    const bool use_panel_ = knobs_.panel; // fused diagonal-block + panel kernels
     bool factor_pass(const double* dE, const double* dD, bool fused, bool tail_fused);
     void enqueue_levels(const PlanView& pv, const TailView& tv, bool fused, hipStream_t s);
     bool finish_pass(bool fused);
@@ -285,15 +297,13 @@ class KktDevice {
     std::vector<int> chunk_ptr_;          // per level: solve chunks [chunk_ptr_[l], chunk_ptr_[l+1])
     std::vector<int> leaf_cnt_;           // per level: leading single-column supernodes of dsweep_sups_
     std::vector<int> leaf8_cnt_;          // per level: the first of them, small leaves (k_fwd_leaf8 / k_bwd_leaf8)
-    bool merge_levels_ = true;            // a level's leaves and other supernodes in one sweep launch (IPO_HIP_MERGE_LEVELS)
-    bool merge_panels_ = true;            // a level's fused and small panels in one launch (k_panel_ws; the same knob)
-    int small_leaves_ = 0;                // levels with at least this many small leaves pack them (IPO_HIP_SMALL_LEAVES; 0: never)
+    int small_leaves() const;             // knobs_.small_leaves, unset: kSmallLeafMinCount
     DevBuf<int> dsweep_sups_;             // level_sups in sweep order (leaves first on unchunked levels)
     DevBuf<int> dchunk_sup_, dchunk_r0_, dsup_chunk0_;
     DevBuf<double> dPartial_;    // backward partial sums, one 64-vector per chunk
     // split-K gather chunks per group (sparse level l, group nlevels = tail)
     bool visits_ = false;
-    int gst_group_ = -1, gst_n_ = 0;   // developer gather stamps (IPO_HIP_GATHER_STAMPS)
+    int gst_group_ = knobs_.gather_stamps, gst_n_ = 0;   // developer gather stamps: one launch, then -1
     DevBuf<long long> dGStamp_;        // deep trees: early gather slots as visits in lower levels' launches
     std::vector<int> ck_kind_;   // per gather group: 0 k_update, 1 k_update_flat, 2 k_update_quad
     std::vector<bool> ck_wide_;   // ck_flat_: k_update_flat (latency-bound launches of deep trees)      // per gather group: k_update<4> (few chunks, units split >= 4 ways)
@@ -307,24 +317,19 @@ class KktDevice {
     DevBuf<SlotRec> dslot_rec_, dtail_slot_rec_;   // per gather k-slot record (sparse units, dense tail)
     DevBuf<unsigned long long> dChainGran_;   // dense-tail sweep chains: z of every block as epoch-tagged granules
     int chain_epoch_ = 0;      // the chains' launch epoch (one per launch, never reused)
-    int visit_blocks_ = kTailVisitBlocks;   // TailView::vk (IPO_HIP_VISIT_BLOCKS)
-    double epsdiag_cap_ = 0.0;     // IPO_HIP_EPSDIAG_MAX (diagnostics; 0: the reference's unbounded growth)
-    int tail_spec_ = 1;            // TailView::dep when the host repair backs it (IPO_HIP_TAIL_SPEC: 0 off, 2 tests)
-    int sparse_dep_ = 1;           // TailView::sdep (IPO_HIP_SPARSE_DEP)
-    bool chain_pairs_ = false; // dense-tail chains with two blocks per workgroup (k_tail_fwd_pair / _bwd_pair)
     bool chain_lead_ = false;  // forward dense-tail sweep by one lead workgroup + helpers (k_tail_fwd_lead)
     DevBuf<int> dtail_task_ptr_, dtail_kslot_, dtail_kslot_ptr_;
     DevBuf<int> dlead_ticket_;         // k_tail_fwd_lead's role tickets (never reset within a run)
     long long lead_ticket_next_ = 0;
-    DevBuf<unsigned> dvisit_list_;     // TailView::vlist (tail_visit_schedule; IPO_HIP_VISIT_SCHED=0: none)
+    DevBuf<unsigned> dvisit_list_;     // TailView::vlist (tail_visit_schedule; knobs_.visit_sched off: none)
     std::vector<int> visit_ptr_;       // TailView::vptr
-    // the dense tail as one persistent launch (k_tail_run; IPO_HIP_TAIL_RUN=0: one launch per step)
+    // the dense tail as one persistent launch (k_tail_run; knobs_.tail_run off: one launch per step)
     bool tail_run_ = false;
     DevBuf<uint2> drun_items_;         // tail_run_schedule
     std::vector<int> run_ptr_;         // first item of each launch
     DevBuf<int> drun_cnt_;             // ticket, pdone[ntb], vseq[ntb * ntb], pread[ntb]
-    // the run's window hand-off (TailRun::pub; IPO_HIP_TAIL_WINPUB=0: off)
-    bool run_winpub_ = true;
+    // the run's window hand-off (TailRun::pub; knobs_.tail_winpub)
+    bool run_winpub_ = false;
     DevBuf<double> drun_pub_;          // [2 * ntb * 4 * kTailPubWin]
     DevBuf<int> drun_wflag_;           // [ntb * ntb * 4], zeroed once
     int run_epoch_ = 0;

@@ -3090,11 +3090,9 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
     if (qb && nforced > 0) throw std::invalid_argument("kkt: a Q block with forced rows is not supported");
     QPattern qpat;
     if (qb) { qpat.kQ = qb->kQ; qpat.iQ = qb->iQ; }
-    // IPO_HIP_SETUP_TIMES: where the host setup goes, to stderr
-    const bool st_on = std::getenv("IPO_HIP_SETUP_TIMES") != nullptr;
     const auto st0 = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
-        if (st_on)
+    auto mark = [&](const char* what) {     // IPO_HIP_SETUP_TIMES: where the host setup goes, to stderr
+        if (knobs_.setup_times)
             std::fprintf(stderr, "setup %-28s %9.1f ms\n", what,
                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - st0).count());
     };
@@ -3107,7 +3105,45 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
     mark("transpose");
     plan_ = build_kkt_plan(m, n, kA, iA, kat.data(), iat.data(), nforced, tail_density, qb ? &qpat : nullptr);
     mark("ordering + symbolic plan");
-    if (nforced > 0) dLinkAx_.alloc(2 * static_cast<size_t>(nforced));
+    // the paths that the knobs and the plan select together
+    visits_ = knobs_.deep_tree(plan_.nlevels);
+    chain_lead_ = knobs_.chain_lead && plan_.nt > 0 && plan_.ntb <= kChainMaxBlocks;
+    tail_run_ = knobs_.tail_run && plan_.nt > 0 && plan_.ntb <= kTailSchedMaxBlocks;
+    run_winpub_ = knobs_.tail_winpub && tail_run_;
+    int dev = 0, cus = 0;
+    IPO_HIP_CHECK(hipGetDevice(&dev));
+    IPO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    upload_plan(kA, iA, A, kat, iat, at, qb);
+    mark("upload_plan");
+    build_panel_units();
+    mark("build_panel_units");
+    build_solve_chunks();
+    mark("build_solve_chunks");
+    build_sweep_order();
+    mark("build_sweep_order");
+    build_sync_free_plan(cus);
+    mark("build_sync_free_plan");
+    const VisitSlots vs = build_visit_slots();
+    mark("build_visit_slots");
+    build_gather_chunks(vs);
+    mark("build_gather_chunks");
+    count_work();
+    mark("count_work");
+    build_slot_records(vs.kslot);
+    mark("build_slot_records");
+    setup_tail(cus);
+    mark("setup_tail");
+    alloc_numeric();
+    mark("alloc_numeric");
+}
+
+// The constraint matrix in both orientations, the Q block and the plan's
+// index arrays.  kat / iat / at and the plan outlive the constructor's first
+// stream synchronisation; the Q diagonal is a local, synchronised here.
+void KktDevice::upload_plan(const int* kA, const int* iA, const double* A, const std::vector<int>& kat,
+                            const std::vector<int>& iat, const std::vector<double>& at, const QBlock* qb) {
+    const int m = m_, n = n_;
+    if (nforced_ > 0) dLinkAx_.alloc(2 * static_cast<size_t>(nforced_));
     const int nz = kA[n];
     hipStream_t s = stream_;
     dkA_.upload(kA, n + 1, s);
@@ -3151,428 +3187,434 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
     dupd_r1_.upload(plan_.upd_r1, s);
     drel_.upload(plan_.rel, s);
     dlevel_sups_.upload(plan_.level_sups, s);
-    mark("fused panel units (k_panel_w");
-    {   // fused panel units (k_panel_w): per supernode max(1, tiles - 1) workgroups,
-        // workgroup j holding the diagonal block and 64-row tile j + 1
-        // (supernodes of at most 16 columns and 64 rows go to the one-wave
-        // small-panel kernel instead: list small_sups_, per level small_ptr_)
-        std::vector<int> fs, fj, ss;
-        fu_ptr_.assign(plan_.nlevels + 1, 0);
-        small_ptr_.assign(plan_.nlevels + 1, 0);
-        for (int l = 0; l < plan_.nlevels; l++) {
-            for (int q = plan_.level_ptr[l]; q < plan_.level_ptr[l + 1]; q++) {
-                const int sp = plan_.level_sups[q];
-                const int nc = plan_.col0[sp + 1] - plan_.col0[sp];
-                const int h = nc + plan_.rowptr[sp + 1] - plan_.rowptr[sp];
-                if (nc <= 16 && h <= kTileRows) { ss.push_back(sp); continue; }
-                const int nw = std::max(1, ceil_div(h, kTileRows) - 1);
-                for (int j = 0; j < nw; j++) { fs.push_back(sp); fj.push_back(j); }
-            }
-            fu_ptr_[l + 1] = static_cast<int>(fs.size());
-            small_ptr_[l + 1] = static_cast<int>(ss.size());
+}
+
+int KktDevice::small_leaves() const { return knobs_.small_leaves < 0 ? kSmallLeafMinCount : knobs_.small_leaves; }
+
+// Fused panel units (k_panel_w): per supernode max(1, tiles - 1) workgroups,
+// workgroup j holding the diagonal block and 64-row tile j + 1
+// (supernodes of at most 16 columns and 64 rows go to the one-wave
+// small-panel kernel instead: list small_sups_, per level small_ptr_)
+void KktDevice::build_panel_units() {
+    hipStream_t s = stream_;
+    std::vector<int> fs, fj, ss;
+    fu_ptr_.assign(plan_.nlevels + 1, 0);
+    small_ptr_.assign(plan_.nlevels + 1, 0);
+    for (int l = 0; l < plan_.nlevels; l++) {
+        for (int q = plan_.level_ptr[l]; q < plan_.level_ptr[l + 1]; q++) {
+            const int sp = plan_.level_sups[q];
+            const int nc = plan_.col0[sp + 1] - plan_.col0[sp];
+            const int h = nc + plan_.rowptr[sp + 1] - plan_.rowptr[sp];
+            if (nc <= 16 && h <= kTileRows) { ss.push_back(sp); continue; }
+            const int nw = std::max(1, ceil_div(h, kTileRows) - 1);
+            for (int j = 0; j < nw; j++) { fs.push_back(sp); fj.push_back(j); }
         }
-        // Levels whose fused units outnumber their supernodes many times
-        // over and fill the device several times (the separator levels of
-        // nested dissection: 1,000-3,500 units, 7-14 per supernode) run the
-        // per-phase kernels instead: the fused units each refactor their
-        // supernode's diagonal block, k_diag factors it once and k_trsm's
-        // tiles only read it.  The same operations on every entry in the
-        // same order (the IPO_HIP_PANEL=0 path), so bitwise the fused one.
-        // IPO_HIP_PANEL_SPLIT: the unit count from which a level splits (0: never)
-        int split_min = 768;
-        if (const char* e = std::getenv("IPO_HIP_PANEL_SPLIT")) split_min = std::max(0, std::atoi(e));
-        split_level_.assign(plan_.nlevels, 0);
-        for (int l = 0; l < plan_.nlevels && split_min > 0; l++) {
-            const int nfu = fu_ptr_[l + 1] - fu_ptr_[l];
-            int nsup = 0;
-            for (int q = fu_ptr_[l]; q < fu_ptr_[l + 1]; q++) nsup += fj[q] == 0;
-            split_level_[l] = nfu >= split_min && nfu >= 4 * nsup;
-        }
-        // single-column small panels of <= 8 rows first in each level's list,
-        // eight to a wave (k_panel_s1) on levels of many of them (the leaf
-        // sweeps' threshold, IPO_HIP_SMALL_LEAVES)
-        small1_cnt_.assign(plan_.nlevels, 0);
-        {
-            int thr = kSmallLeafMinCount;
-            if (const char* e = std::getenv("IPO_HIP_SMALL_LEAVES")) thr = std::max(0, std::atoi(e));
-            for (int l = 0; l < plan_.nlevels && thr > 0; l++) {
-                const auto b = ss.begin() + small_ptr_[l], e = ss.begin() + small_ptr_[l + 1];
-                const auto mid = std::stable_partition(b, e, [&](int sp) {
-                    return plan_.col0[sp + 1] - plan_.col0[sp] == 1 && 1 + plan_.rowptr[sp + 1] - plan_.rowptr[sp] <= 8;
-                });
-                if (mid - b >= thr) small1_cnt_[l] = static_cast<int>(mid - b);
-            }
-        }
-        dfu_sup_.upload(fs, s);
-        dfu_j_.upload(fj, s);
-        dsmall_sups_.upload(ss, s);
-        IPO_HIP_CHECK(hipStreamSynchronize(s));
-        // IPO_HIP_PANEL=0: per-phase kernels only (k_diag + k_trsm + k_tail_syrk,
-        // the dependent-pivot path), the bitwise reference of the fused ones
-        if (const char* e = std::getenv("IPO_HIP_PANEL")) use_panel_ = std::atoi(e) != 0;
+        fu_ptr_[l + 1] = static_cast<int>(fs.size());
+        small_ptr_[l + 1] = static_cast<int>(ss.size());
     }
-    mark("solve chunks: levels holding");
-    {   // solve chunks: levels holding a panel with more than kChunkRows rows below
-        // its diagonal block are solved in 64-row chunks (two launches each way)
-        constexpr int kChunkRows = 128;
-        std::vector<int> csup, cr0, chunk0(plan_.nsup, -1);
-        chunk_ptr_.assign(plan_.nlevels + 1, 0);
-        for (int l = 0; l < plan_.nlevels; l++) {
-            bool big = false;
-            for (int q = plan_.level_ptr[l]; q < plan_.level_ptr[l + 1]; q++) {
-                const int sp = plan_.level_sups[q];
-                big |= plan_.rowptr[sp + 1] - plan_.rowptr[sp] > kChunkRows;
-            }
-            if (big)
-                for (int q = plan_.level_ptr[l]; q < plan_.level_ptr[l + 1]; q++) {
-                    const int sp = plan_.level_sups[q], hb = plan_.rowptr[sp + 1] - plan_.rowptr[sp];
-                    chunk0[sp] = static_cast<int>(csup.size());
-                    for (int r0 = 0; r0 < hb; r0 += 64) { csup.push_back(sp); cr0.push_back(r0); }
-                }
-            chunk_ptr_[l + 1] = static_cast<int>(csup.size());
-        }
-        dchunk_sup_.upload(csup, s);
-        dchunk_r0_.upload(cr0, s);
-        dsup_chunk0_.upload(chunk0, s);
-        partial_stride_ = csup.empty() ? 1 : csup.size() * kPanelCols;
-        dPartial_.alloc(2 * partial_stride_);
-        IPO_HIP_CHECK(hipStreamSynchronize(s));   // csup / cr0 / chunk0 are stack vectors
-        h_chunk0_ = chunk0;
+    // Levels whose fused units outnumber their supernodes many times
+    // over and fill the device several times (the separator levels of
+    // nested dissection: 1,000-3,500 units, 7-14 per supernode) run the
+    // per-phase kernels instead: the fused units each refactor their
+    // supernode's diagonal block, k_diag factors it once and k_trsm's
+    // tiles only read it.  The same operations on every entry in the
+    // same order (the IPO_HIP_PANEL=0 path), so bitwise the fused one.
+    // IPO_HIP_PANEL_SPLIT: the unit count from which a level splits (0: never)
+    const int split_min = knobs_.panel_split;
+    split_level_.assign(plan_.nlevels, 0);
+    for (int l = 0; l < plan_.nlevels && split_min > 0; l++) {
+        const int nfu = fu_ptr_[l + 1] - fu_ptr_[l];
+        int nsup = 0;
+        for (int q = fu_ptr_[l]; q < fu_ptr_[l + 1]; q++) nsup += fj[q] == 0;
+        split_level_[l] = nfu >= split_min && nfu >= 4 * nsup;
     }
-    mark("sweep order of each level");
-    {   // sweep order of each level: on levels without solve chunks the
-        // single-column supernodes with <= 64 rows below come first (one wave
-        // each, k_fwd_leaf / k_bwd_leaf), the rest after them
-        std::vector<int> ss(plan_.level_sups);
-        leaf_cnt_.assign(plan_.nlevels, 0);
-        leaf8_cnt_.assign(plan_.nlevels, 0);
-        small_leaves_ = kSmallLeafMinCount;
-        if (const char* e = std::getenv("IPO_HIP_MERGE_LEVELS")) merge_levels_ = merge_panels_ = std::atoi(e) != 0;
-        if (const char* e = std::getenv("IPO_HIP_SMALL_LEAVES")) small_leaves_ = std::max(0, std::atoi(e));
-        for (int l = 0; l < plan_.nlevels; l++) {
-            if (chunk_ptr_[l + 1] > chunk_ptr_[l]) continue;
-            const auto b = ss.begin() + plan_.level_ptr[l], e = ss.begin() + plan_.level_ptr[l + 1];
-            const auto mid = std::stable_partition(b, e, [&](int sp) {
-                return plan_.col0[sp + 1] - plan_.col0[sp] == 1 && plan_.rowptr[sp + 1] - plan_.rowptr[sp] <= 64;
+    // single-column small panels of <= 8 rows first in each level's list,
+    // eight to a wave (k_panel_s1) on levels of many of them (the leaf
+    // sweeps' threshold, IPO_HIP_SMALL_LEAVES)
+    small1_cnt_.assign(plan_.nlevels, 0);
+    const int thr = small_leaves();
+    for (int l = 0; l < plan_.nlevels && thr > 0; l++) {
+        const auto b = ss.begin() + small_ptr_[l], e = ss.begin() + small_ptr_[l + 1];
+        const auto mid = std::stable_partition(b, e, [&](int sp) {
+            return plan_.col0[sp + 1] - plan_.col0[sp] == 1 && 1 + plan_.rowptr[sp + 1] - plan_.rowptr[sp] <= 8;
+        });
+        if (mid - b >= thr) small1_cnt_[l] = static_cast<int>(mid - b);
+    }
+    dfu_sup_.upload(fs, s);
+    dfu_j_.upload(fj, s);
+    dsmall_sups_.upload(ss, s);
+    IPO_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// Solve chunks: levels holding a panel with more than kChunkRows rows below
+// its diagonal block are solved in 64-row chunks (two launches each way)
+void KktDevice::build_solve_chunks() {
+    hipStream_t s = stream_;
+    constexpr int kChunkRows = 128;
+    std::vector<int> csup, cr0, chunk0(plan_.nsup, -1);
+    chunk_ptr_.assign(plan_.nlevels + 1, 0);
+    for (int l = 0; l < plan_.nlevels; l++) {
+        bool big = false;
+        for (int q = plan_.level_ptr[l]; q < plan_.level_ptr[l + 1]; q++) {
+            const int sp = plan_.level_sups[q];
+            big |= plan_.rowptr[sp + 1] - plan_.rowptr[sp] > kChunkRows;
+        }
+        if (big)
+            for (int q = plan_.level_ptr[l]; q < plan_.level_ptr[l + 1]; q++) {
+                const int sp = plan_.level_sups[q], hb = plan_.rowptr[sp + 1] - plan_.rowptr[sp];
+                chunk0[sp] = static_cast<int>(csup.size());
+                for (int r0 = 0; r0 < hb; r0 += 64) { csup.push_back(sp); cr0.push_back(r0); }
+            }
+        chunk_ptr_[l + 1] = static_cast<int>(csup.size());
+    }
+    dchunk_sup_.upload(csup, s);
+    dchunk_r0_.upload(cr0, s);
+    dsup_chunk0_.upload(chunk0, s);
+    partial_stride_ = csup.empty() ? 1 : csup.size() * kPanelCols;
+    dPartial_.alloc(2 * partial_stride_);
+    IPO_HIP_CHECK(hipStreamSynchronize(s));   // csup / cr0 / chunk0 are stack vectors
+    h_chunk0_ = chunk0;
+}
+
+// Sweep order of each level: on levels without solve chunks the
+// single-column supernodes with <= 64 rows below come first (one wave
+// each, k_fwd_leaf / k_bwd_leaf), the rest after them
+void KktDevice::build_sweep_order() {
+    hipStream_t s = stream_;
+    std::vector<int> ss(plan_.level_sups);
+    leaf_cnt_.assign(plan_.nlevels, 0);
+    leaf8_cnt_.assign(plan_.nlevels, 0);
+    const int min8 = small_leaves();
+    for (int l = 0; l < plan_.nlevels; l++) {
+        if (chunk_ptr_[l + 1] > chunk_ptr_[l]) continue;
+        const auto b = ss.begin() + plan_.level_ptr[l], e = ss.begin() + plan_.level_ptr[l + 1];
+        const auto mid = std::stable_partition(b, e, [&](int sp) {
+            return plan_.col0[sp + 1] - plan_.col0[sp] == 1 && plan_.rowptr[sp + 1] - plan_.rowptr[sp] <= 64;
+        });
+        leaf_cnt_[l] = static_cast<int>(mid - b);
+        if (min8 > 0) {   // the small ones first (k_fwd_leaf8 / k_bwd_leaf8)
+            const auto mid8 = std::stable_partition(b, mid, [&](int sp) {
+                const int c = plan_.col0[sp];
+                return plan_.rowptr[sp + 1] - plan_.rowptr[sp] <= kSmallLeaf &&
+                       plan_.yrow_ptr[c + 1] - plan_.yrow_ptr[c] <= kSmallLeaf;
             });
-            leaf_cnt_[l] = static_cast<int>(mid - b);
-            if (small_leaves_ > 0) {   // the small ones first (k_fwd_leaf8 / k_bwd_leaf8)
-                const auto mid8 = std::stable_partition(b, mid, [&](int sp) {
-                    const int c = plan_.col0[sp];
-                    return plan_.rowptr[sp + 1] - plan_.rowptr[sp] <= kSmallLeaf &&
-                           plan_.yrow_ptr[c + 1] - plan_.yrow_ptr[c] <= kSmallLeaf;
-                });
-                leaf8_cnt_[l] = static_cast<int>(mid8 - b);
-                // a wave of eight leaves touches eight times the cache lines
-                // per load: slower on latency-bound levels (dfl001's sweeps
-                // 4 ms slower per solve), faster from tens of thousands of
-                // leaves on (configs[3]: 10^6)
-                if (leaf8_cnt_[l] < small_leaves_) leaf8_cnt_[l] = 0;
+            leaf8_cnt_[l] = static_cast<int>(mid8 - b);
+            // a wave of eight leaves touches eight times the cache lines
+            // per load: slower on latency-bound levels (dfl001's sweeps
+            // 4 ms slower per solve), faster from tens of thousands of
+            // leaves on (configs[3]: 10^6)
+            if (leaf8_cnt_[l] < min8) leaf8_cnt_[l] = 0;
+        }
+    }
+    dsweep_sups_.upload(ss, s);
+    IPO_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// Deep elimination trees (at least kVisitLevels levels, e.g. the banded
+// BASELINE configs[3]: 2,785 levels, most of them one or two 64-column
+// supernodes): a level's gather would wait on every descendant's update,
+// although 93 % of its k-slots come from supernodes finished several
+// levels earlier.  There each unit's slots are ordered by the level of
+// their source (stable), and only the slabs that hold a source of the
+// level just below ("late") stay in the unit's own level's gather; the
+// earlier slabs become visits of at most kVisitSlots slots, scheduled as
+// late as their sources allow into the gather launches of the levels
+// below (one visit per unit per launch, each a read-modify-write of the
+// unit's tile in slot order).  The level chain then waits per level on
+// one small gather and the panel, the visits ride in the same launches
+// beside them.  IPO_HIP_VISITS=1/0 forces the schedule on / off
+// (KktKnobs::deep_tree); without it the result is empty.
+KktDevice::VisitSlots KktDevice::build_visit_slots() const {
+    VisitSlots v;
+    v.vis.resize(plan_.nlevels + 1);
+    if (!visits_) return v;
+    const int nu = static_cast<int>(plan_.unit_sup.size());
+    const int visit_slabs = knobs_.visit_slabs;
+    v.kptr.assign(nu + 1, 0);
+    v.late_b.assign(nu, 0);
+    std::vector<std::pair<int, int>> sl;   // (source level, slot)
+    std::vector<int> rl;
+    for (int l = 1; l < plan_.nlevels; l++)
+        for (int u = plan_.unit_level_ptr[l]; u < plan_.unit_level_ptr[l + 1]; u++) {
+            sl.clear();
+            for (int i = plan_.kslot_ptr[u]; i < plan_.kslot_ptr[u + 1]; i++) {
+                const int k = plan_.kslot[i];
+                if (k >= 0) sl.push_back({plan_.level[plan_.utasks[k >> 6].src], k});
+            }
+            std::stable_sort(sl.begin(), sl.end(),
+                             [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
+            const int kb = static_cast<int>(v.kslot.size());
+            rl.clear();
+            for (size_t i = 0; i < sl.size(); i++) {
+                v.kslot.push_back(sl[i].second);
+                if (i % kSlab == 0) rl.push_back(sl[i].first);
+                else rl.back() = std::max(rl.back(), sl[i].first);
+            }
+            while (v.kslot.size() % kSlab) v.kslot.push_back(-1);
+            v.kptr[u + 1] = static_cast<int>(v.kslot.size());
+            const int nsl = static_cast<int>(rl.size());
+            int j = nsl;
+            while (j > 0 && rl[j - 1] >= l - 1) j--;
+            v.late_b[u] = kb + kSlab * j;
+            // early slabs [0, j), backwards, as late as their sources allow
+            int t = l - 1, end = j, cur = j;
+            while (cur > 0) {
+                if (end - cur >= visit_slabs && rl[cur - 1] <= t - 2) {
+                    v.vis[t].push_back(make_int3(u, kb + kSlab * cur, kb + kSlab * end));
+                    t--;
+                    end = cur;
+                }
+                cur--;
+            }
+            if (end > 0) v.vis[t].push_back(make_int3(u, kb, kb + kSlab * end));
+        }
+    // groups visit their units in unit order
+    for (auto& g : v.vis)
+        std::sort(g.begin(), g.end(), [](const int3& a, const int3& b) { return a.x < b.x; });
+    return v;
+}
+
+// Gather chunks (split K): groups = sparse levels (with their visits, vs),
+// then the dense tail
+void KktDevice::build_gather_chunks(const VisitSlots& vs) {
+    hipStream_t s = stream_;
+    // flat gathers (k_update_flat) for the latency-bound launches of
+    // deep trees: IPO_HIP_GATHER_FLAT=0 never, 1 (default) deep trees,
+    // 2 every launch of at most kFlatMaxChunks chunks
+    const int flat_mode = knobs_.gather_flat;
+    // quadrant gathers (k_update_quad) on the narrow levels of deep trees
+    // (IPO_HIP_GATHER_QUAD=0: off)
+    const bool quad_mode = knobs_.gather_quad;
+    std::vector<int> cu, cb, ce, cp, cq, su, sp0, sn;
+    ck_ptr_.assign(plan_.nlevels + 2, 0);
+    sp_ptr_.assign(plan_.nlevels + 2, 0);
+    size_t max_part = 0;
+    const int wg_target = 512;
+    const int min_chunk = knobs_.min_chunk;
+    // units [u0, u1), slots [kbeg(u), kend(u)) each, then the group's visits
+    // a sparse unit's 32 x 32 quadrants that hold lower-triangle entries (k_update_quad)
+    auto quadrants = [&](int u, int kb, int ke) {
+        const int sp = plan_.unit_sup[u], t = plan_.unit_tile[u];
+        const int nc = plan_.col0[sp + 1] - plan_.col0[sp], h = nc + plan_.rowptr[sp + 1] - plan_.rowptr[sp];
+        const int nrow = std::min(kTileRows, h - t * kTileRows);
+        for (int q = 0; q < 4; q++) {
+            const int qr = q & 1, qc = q >> 1;
+            if (32 * qr >= nrow || 32 * qc >= nc || (t == 0 && qc > qr)) continue;
+            cu.push_back(u); cb.push_back(kb); ce.push_back(ke); cp.push_back(-1 - q); cq.push_back(-1);
+        }
+    };
+    auto group = [&](int u0, int u1, auto kbeg, auto kend, const std::vector<int3>* visits) {
+        const long nck0 = static_cast<long>(cu.size());
+        long sumk = 0, nun = 0;
+        for (int u = u0; u < u1; u++) { sumk += kend(u) - kbeg(u); nun += kend(u) > kbeg(u); }
+        // deep trees' narrow levels: quadrant gathers, one chunk per unit
+        const bool quad = quad_mode && visits && nun + static_cast<long>(visits->size()) <= kQuadMaxUnits;
+        if (quad) {
+            for (int u = u0; u < u1; u++)
+                if (kend(u) > kbeg(u)) quadrants(u, kbeg(u), kend(u));
+            for (const int3& v : *visits) quadrants(v.x, v.y, v.z);
+            ck_wide_.push_back(false);
+            ck_kind_.push_back(2);
+            return;
+        }
+        // aim at >= wg_target workgroups per launch, chunks of min_chunk..512 slots
+        long kmax = (sumk / wg_target + kSlab - 1) / kSlab * kSlab;
+        kmax = std::max<long>(min_chunk, std::min<long>(kMaxChunkSlots, kmax));
+        int np = 0, mx = 0;
+        for (int u = u0; u < u1; u++) {
+            const int kb = kbeg(u), ke = kend(u);
+            if (ke == kb) continue;
+            const int nch = static_cast<int>((ke - kb + kmax - 1) / kmax);
+            mx = std::max(mx, nch);
+            if (nch > 1) { su.push_back(u); sp0.push_back(np); sn.push_back(nch); }
+            for (int j = 0; j < nch; j++) {
+                cu.push_back(u);
+                cb.push_back(kb + static_cast<int>(j * kmax));
+                ce.push_back(std::min<int>(ke, kb + static_cast<int>((j + 1) * kmax)));
+                cp.push_back(nch > 1 ? np++ : -1);
+                cq.push_back(nch > 1 ? static_cast<int>(su.size()) - 1 : -1);
             }
         }
-        dsweep_sups_.upload(ss, s);
+        if (visits)
+            for (const int3& v : *visits) {
+                cu.push_back(v.x); cb.push_back(v.y); ce.push_back(v.z); cp.push_back(-1); cq.push_back(-1);
+            }
+        max_part = std::max<size_t>(max_part, np);
+        // a group of few chunks (about one per CU: occupancy does not
+        // matter) whose units are split many ways waits on its partial
+        // sums: sum them several at a time
+        ck_wide_.push_back(mx >= 4 && static_cast<long>(cu.size()) - nck0 <= 512);
+        ck_kind_.push_back(quad ? 2 : (flat_mode == 2 || (flat_mode == 1 && visits_)) &&
+                                           static_cast<long>(cu.size()) - nck0 <= kFlatMaxChunks ? 1 : 0);
+    };
+    const std::vector<int>& kp = plan_.kslot_ptr;
+    ck_wide_.clear();
+    ck_kind_.clear();
+    for (int l = 0; l < plan_.nlevels; l++) {
+        if (l == 0) { ck_wide_.push_back(false); ck_kind_.push_back(0); }
+        else if (visits_)
+            group(plan_.unit_level_ptr[l], plan_.unit_level_ptr[l + 1], [&](int u) { return vs.late_b[u]; },
+                  [&](int u) { return vs.kptr[u + 1]; }, &vs.vis[l]);
+        else
+            group(plan_.unit_level_ptr[l], plan_.unit_level_ptr[l + 1], [&](int u) { return kp[u]; },
+                  [&](int u) { return kp[u + 1]; }, nullptr);
+        ck_ptr_[l + 1] = static_cast<int>(cu.size());
+        sp_ptr_[l + 1] = static_cast<int>(su.size());
+    }
+    const std::vector<int>& tp = plan_.tail_kslot_ptr;
+    if (plan_.nt > 0)
+        group(0, plan_.ntb * (plan_.ntb + 1) / 2, [&](int u) { return tp[u]; }, [&](int u) { return tp[u + 1]; },
+              nullptr);
+    else { ck_wide_.push_back(false); ck_kind_.push_back(0); }
+    ck_ptr_[plan_.nlevels + 1] = static_cast<int>(cu.size());
+    sp_ptr_[plan_.nlevels + 1] = static_cast<int>(su.size());
+    dck_u_.upload(cu, s);
+    dck_b_.upload(cb, s);
+    dck_e_.upload(ce, s);
+    dck_part_.upload(cp, s);
+    dsp_u_.upload(su, s);
+    dsp_p0_.upload(sp0, s);
+    dsp_n_.upload(sn, s);
+    dck_q_.upload(cq, s);
+    dSplitCnt_.alloc(std::max<size_t>(1, su.size()));
+    IPO_HIP_CHECK(hipMemsetAsync(dSplitCnt_.get(), 0, std::max<size_t>(1, su.size()) * sizeof(int), s));
+    dPartialTile_.alloc(std::max<size_t>(1, max_part) * (kTileRows * kTileRows + 4 * kTileRows));
+    IPO_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// Launches per sweep and algorithmic work per phase occurrence
+void KktDevice::count_work() {
+    fwd_launches_ = bwd_launches_ = sf_level_ < plan_.nlevels ? 1 : 0;
+    for (int l = 0; l < sf_level_; l++) {
+        const int nsl = plan_.level_ptr[l + 1] - plan_.level_ptr[l];
+        const int nl = leaf_cnt_[l], n8 = leaf8_cnt_[l];
+        const int k = chunk_ptr_[l + 1] > chunk_ptr_[l] ? 2
+                    : (n8 > 0) + (nl > n8 && nsl > nl && knobs_.merge_levels ? 1 : (nl > n8) + (nsl > nl));
+        fwd_launches_ += k;
+        bwd_launches_ += k;
+    }
+    if (plan_.nt > 0) {
+        const int chain = plan_.ntb <= kChainMaxBlocks;
+        fwd_launches_ += 1 + (chain ? 1 : plan_.ntb);
+        bwd_launches_ += chain ? 1 : 1 + plan_.ntb;
+    }
+    const auto& P = plan_;
+    double gf = 0, gb = 0;
+    auto tasks_work = [&](const std::vector<TailTask>& ts) {
+        for (const TailTask& t : ts) {
+            const double ncd = P.col0[t.src + 1] - P.col0[t.src];
+            const double nr = __builtin_popcountll(t.rmask), ncl = __builtin_popcountll(t.cmask);
+            gf += 2.0 * ncd * nr * ncl;
+            gb += 8.0 * ncd * (nr + ncl);
+        }
+    };
+    tasks_work(P.utasks);
+    tasks_work(P.tail_tasks);
+    double df = 0, db = 0, tf = 0, tb = 0, sf = 0, sb = 0, lxs = 0;
+    for (int sp = 0; sp < P.nsup; sp++) {
+        const double nc = P.col0[sp + 1] - P.col0[sp], hb = P.rowptr[sp + 1] - P.rowptr[sp];
+        df += 2.0 * nc * nc * nc / 3.0;
+        db += 8.0 * 1.5 * nc * nc;
+        tf += hb * nc * nc;
+        tb += 16.0 * hb * nc;
+        lxs += (nc + hb) * nc;
+        gb += 16.0 * (nc + hb) * nc;      // read-modify-write of every target panel
+    }
+    const double sdf = df, sdb = db, stf = tf, stb = tb;     // sparse panels alone
+    for (int kb = 0; kb < P.ntb; kb++) {
+        const double nc = std::min(kPanelCols, P.nt - kb * kPanelCols), below = P.nt - kb * kPanelCols - nc;
+        df += 2.0 * nc * nc * nc / 3.0;
+        db += 8.0 * 1.5 * nc * nc;
+        tf += below * nc * nc;
+        tb += 16.0 * below * nc;                                // L21 read + write
+        const double nb = P.ntb - kb - 1;
+        sf += 2.0 * nc * (nb * (nb + 1) / 2) * kTileRows * kTileRows;
+        sb += (nb * (nb + 1) / 2) * (16.0 * kTileRows * kTileRows + 16.0 * kTileRows * nc);
+    }
+    gb += 16.0 * 0.5 * P.nt * P.nt;                                 // tail block read-modify-write
+    work_flops[kPhGather] = gf; work_bytes[kPhGather] = gb;
+    work_flops[kPhDiag] = df; work_bytes[kPhDiag] = db;
+    work_flops[kPhTrsm] = tf; work_bytes[kPhTrsm] = tb;
+    work_flops[kPhSyrk] = sf; work_bytes[kPhSyrk] = sb;
+    // Algorithmic flops per factorisation in SURVEY.md 8(d)'s unit: the
+    // reference's narth (ldlt.c:1243-1248), split by the phase doing each
+    // column's work (kkt_plan.h: narth_tail / narth_gather / narth_panel,
+    // which sum to narth).  What the kernels execute (plan flops above,
+    // the dense tail's explicit zeros) is not the work.  Bytes: each
+    // phase's entries of L read and written once (+ the gather's source
+    // reads from the plan).
+    (void)sdf; (void)stf; (void)df; (void)tf; (void)sf; (void)lxs;
+    work_flops[kPhGather] = P.narth_gather;
+    if (use_panel_) {   // k_panel_w does both: the diag phase carries the sparse trsm work;
+        // the dense tail is its own phase (k_tail_pr: panels + deferred
+        // trailing updates; its repair launches)
+        work_flops[kPhDiag] = P.narth_panel; work_bytes[kPhDiag] = sdb + stb;
+        work_flops[kPhTrsm] = work_bytes[kPhTrsm] = 0;
+        work_flops[kPhSyrk] = work_bytes[kPhSyrk] = 0;
+        work_flops[kPhTail] = P.narth_tail;
+        work_bytes[kPhTail] = 16.0 * (static_cast<double>(P.lnz_tail) + P.nt);
+    } else {            // per-phase path: the tail's work goes with its trailing updates
+        work_flops[kPhDiag] = P.narth_panel;
+        work_flops[kPhTrsm] = 0;
+        work_flops[kPhSyrk] = P.narth_tail;
+    }
+    // a sweep (s (4 nnz(L) + N) per iteration, a solve
+    // being one forward and one backward sweep): 2 nnz(L) + N / 2 flops,
+    // every entry of L read once (12 B with its index) and the vector
+    // values in and out
+    for (int ph : {kPhForward, kPhBackward}) {
+        work_flops[ph] = 2.0 * static_cast<double>(P.lnz) + 0.5 * T_;
+        work_bytes[ph] = 12.0 * static_cast<double>(P.lnz) + 16.0 * T_;
+    }
+}
+
+// Per-task source descriptors and per-slot records of the gather; kslot_v:
+// the sparse units' slots in visit order (build_gather_chunks)
+void KktDevice::build_slot_records(const std::vector<int>& kslot_v) {
+    hipStream_t s = stream_;
+    auto build = [&](const std::vector<TailTask>& ts, DevBuf<TaskSrc>& dst) {
+        std::vector<TaskSrc> v(ts.size());
+        for (size_t t = 0; t < ts.size(); t++) {
+            const int d = ts[t].src, ncd = plan_.col0[d + 1] - plan_.col0[d];
+            v[t].colbase = plan_.off[d] + ncd;
+            v[t].hd = ncd + (plan_.rowptr[d + 1] - plan_.rowptr[d]);
+            v[t].cd0 = plan_.col0[d];
+        }
+        dst.upload(v, s);
         IPO_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    dyrow_ptr_.upload(plan_.yrow_ptr, s);
-    build_sync_free_plan();
-    // Deep elimination trees (at least kVisitLevels levels, e.g. the banded
-    // BASELINE configs[3]: 2,785 levels, most of them one or two 64-column
-    // supernodes): a level's gather would wait on every descendant's update,
-    // although 93 % of its k-slots come from supernodes finished several
-    // levels earlier.  There each unit's slots are ordered by the level of
-    // their source (stable), and only the slabs that hold a source of the
-    // level just below ("late") stay in the unit's own level's gather; the
-    // earlier slabs become visits of at most kVisitSlots slots, scheduled as
-    // late as their sources allow into the gather launches of the levels
-    // below (one visit per unit per launch, each a read-modify-write of the
-    // unit's tile in slot order).  The level chain then waits per level on
-    // one small gather and the panel, the visits ride in the same launches
-    // beside them.  IPO_HIP_VISITS=1/0 forces the schedule on / off.
-    std::vector<int> kslot_v;
-    mark("gather chunks (split K)");
-    {   // gather chunks (split K): groups = sparse levels, then the dense tail
-        const int nu = static_cast<int>(plan_.unit_sup.size());
-        const char* ve = std::getenv("IPO_HIP_VISITS");
-        visits_ = ve ? std::atoi(ve) != 0 : plan_.nlevels >= kVisitLevels;
-        // flat gathers (k_update_flat) for the latency-bound launches of
-        // deep trees: IPO_HIP_GATHER_FLAT=0 never, 1 (default) deep trees,
-        // 2 every launch of at most kFlatMaxChunks chunks
-        int flat_mode = 1;
-        if (const char* e = std::getenv("IPO_HIP_GATHER_STAMPS")) gst_group_ = std::atoi(e);
-        // quadrant gathers (k_update_quad) on the narrow levels of deep trees
-        // (IPO_HIP_GATHER_QUAD=0: off)
-        bool quad_mode = true;
-        if (const char* e = std::getenv("IPO_HIP_GATHER_QUAD")) quad_mode = std::atoi(e) != 0;
-        if (const char* e = std::getenv("IPO_HIP_GATHER_FLAT")) flat_mode = std::atoi(e);
-        int visit_slabs = kVisitSlots / kSlab;
-        if (const char* e = std::getenv("IPO_HIP_VISIT_SLOTS")) visit_slabs = std::max(1, std::atoi(e) / kSlab);
-        std::vector<int> kptr_v, late_b;
-        std::vector<std::vector<int3>> vis(plan_.nlevels + 1);   // per group: (unit, slot begin, slot end)
-        if (visits_) {
-            kptr_v.assign(nu + 1, 0);
-            late_b.assign(nu, 0);
-            std::vector<std::pair<int, int>> sl;   // (source level, slot)
-            std::vector<int> rl;
-            for (int l = 1; l < plan_.nlevels; l++)
-                for (int u = plan_.unit_level_ptr[l]; u < plan_.unit_level_ptr[l + 1]; u++) {
-                    sl.clear();
-                    for (int i = plan_.kslot_ptr[u]; i < plan_.kslot_ptr[u + 1]; i++) {
-                        const int k = plan_.kslot[i];
-                        if (k >= 0) sl.push_back({plan_.level[plan_.utasks[k >> 6].src], k});
-                    }
-                    std::stable_sort(sl.begin(), sl.end(),
-                                     [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
-                    const int kb = static_cast<int>(kslot_v.size());
-                    rl.clear();
-                    for (size_t i = 0; i < sl.size(); i++) {
-                        kslot_v.push_back(sl[i].second);
-                        if (i % kSlab == 0) rl.push_back(sl[i].first);
-                        else rl.back() = std::max(rl.back(), sl[i].first);
-                    }
-                    while (kslot_v.size() % kSlab) kslot_v.push_back(-1);
-                    kptr_v[u + 1] = static_cast<int>(kslot_v.size());
-                    const int nsl = static_cast<int>(rl.size());
-                    int j = nsl;
-                    while (j > 0 && rl[j - 1] >= l - 1) j--;
-                    late_b[u] = kb + kSlab * j;
-                    // early slabs [0, j), backwards, as late as their sources allow
-                    int t = l - 1, end = j, cur = j;
-                    while (cur > 0) {
-                        if (end - cur >= visit_slabs && rl[cur - 1] <= t - 2) {
-                            vis[t].push_back(make_int3(u, kb + kSlab * cur, kb + kSlab * end));
-                            t--;
-                            end = cur;
-                        }
-                        cur--;
-                    }
-                    if (end > 0) vis[t].push_back(make_int3(u, kb, kb + kSlab * end));
-                }
-            // groups visit their units in unit order
-            for (auto& g : vis)
-                std::sort(g.begin(), g.end(), [](const int3& a, const int3& b) { return a.x < b.x; });
+    };
+    build(plan_.utasks, dusrc_);
+    if (plan_.nt > 0) build(plan_.tail_tasks, dtsrc_);
+    // per k-slot records of the gather (SlotRec), expanded from the
+    // slot -> task -> source panel indirection
+    auto expand = [&](const std::vector<int>& kslot, const std::vector<TailTask>& ts, DevBuf<SlotRec>& dst) {
+        std::vector<SlotRec> v(kslot.size());
+        for (size_t i = 0; i < kslot.size(); i++) {
+            const int sl = kslot[i];
+            SlotRec& r = v[i];
+            if (sl < 0) { r.rmask = r.cmask = 0; r.roff = 0; r.cdelta = 0; r.dk = 0; continue; }
+            const TailTask& t = ts[sl >> 6];
+            const int kl = sl & 63, d = t.src, ncd = plan_.col0[d + 1] - plan_.col0[d];
+            const int64_t hd = ncd + (plan_.rowptr[d + 1] - plan_.rowptr[d]);
+            r.rmask = t.rmask;
+            r.cmask = t.cmask;
+            r.roff = plan_.off[d] + ncd + kl * hd + t.rbase;
+            r.cdelta = t.cbase - t.rbase;
+            r.dk = plan_.col0[d] + kl;
         }
-        std::vector<int> cu, cb, ce, cp, cq, su, sp0, sn;
-        ck_ptr_.assign(plan_.nlevels + 2, 0);
-        sp_ptr_.assign(plan_.nlevels + 2, 0);
-        size_t max_part = 0;
-        const int wg_target = 512;
-        int min_chunk = 64;     // 64: measured best of 16-256 on configs[3] and dfl001 (IPO_HIP_MIN_CHUNK)
-        if (const char* e = std::getenv("IPO_HIP_MIN_CHUNK")) min_chunk = std::max(kSlab, std::atoi(e) / kSlab * kSlab);
-        // units [u0, u1), slots [kbeg(u), kend(u)) each, then the group's visits
-        // a sparse unit's 32 x 32 quadrants that hold lower-triangle entries (k_update_quad)
-        auto quadrants = [&](int u, int kb, int ke) {
-            const int sp = plan_.unit_sup[u], t = plan_.unit_tile[u];
-            const int nc = plan_.col0[sp + 1] - plan_.col0[sp], h = nc + plan_.rowptr[sp + 1] - plan_.rowptr[sp];
-            const int nrow = std::min(kTileRows, h - t * kTileRows);
-            for (int q = 0; q < 4; q++) {
-                const int qr = q & 1, qc = q >> 1;
-                if (32 * qr >= nrow || 32 * qc >= nc || (t == 0 && qc > qr)) continue;
-                cu.push_back(u); cb.push_back(kb); ce.push_back(ke); cp.push_back(-1 - q); cq.push_back(-1);
-            }
-        };
-        auto group = [&](int u0, int u1, auto kbeg, auto kend, const std::vector<int3>* visits) {
-            const long nck0 = static_cast<long>(cu.size());
-            long sumk = 0, nun = 0;
-            for (int u = u0; u < u1; u++) { sumk += kend(u) - kbeg(u); nun += kend(u) > kbeg(u); }
-            // deep trees' narrow levels: quadrant gathers, one chunk per unit
-            const bool quad = quad_mode && visits && nun + static_cast<long>(visits->size()) <= kQuadMaxUnits;
-            if (quad) {
-                for (int u = u0; u < u1; u++)
-                    if (kend(u) > kbeg(u)) quadrants(u, kbeg(u), kend(u));
-                for (const int3& v : *visits) quadrants(v.x, v.y, v.z);
-                ck_wide_.push_back(false);
-                ck_kind_.push_back(2);
-                return;
-            }
-            // aim at >= wg_target workgroups per launch, chunks of min_chunk..512 slots
-            long kmax = (sumk / wg_target + kSlab - 1) / kSlab * kSlab;
-            kmax = std::max<long>(min_chunk, std::min<long>(kMaxChunkSlots, kmax));
-            int np = 0, mx = 0;
-            for (int u = u0; u < u1; u++) {
-                const int kb = kbeg(u), ke = kend(u);
-                if (ke == kb) continue;
-                const int nch = static_cast<int>((ke - kb + kmax - 1) / kmax);
-                mx = std::max(mx, nch);
-                if (nch > 1) { su.push_back(u); sp0.push_back(np); sn.push_back(nch); }
-                for (int j = 0; j < nch; j++) {
-                    cu.push_back(u);
-                    cb.push_back(kb + static_cast<int>(j * kmax));
-                    ce.push_back(std::min<int>(ke, kb + static_cast<int>((j + 1) * kmax)));
-                    cp.push_back(nch > 1 ? np++ : -1);
-                    cq.push_back(nch > 1 ? static_cast<int>(su.size()) - 1 : -1);
-                }
-            }
-            if (visits)
-                for (const int3& v : *visits) {
-                    cu.push_back(v.x); cb.push_back(v.y); ce.push_back(v.z); cp.push_back(-1); cq.push_back(-1);
-                }
-            max_part = std::max<size_t>(max_part, np);
-            // a group of few chunks (about one per CU: occupancy does not
-            // matter) whose units are split many ways waits on its partial
-            // sums: sum them several at a time
-            ck_wide_.push_back(mx >= 4 && static_cast<long>(cu.size()) - nck0 <= 512);
-            ck_kind_.push_back(quad ? 2 : (flat_mode == 2 || (flat_mode == 1 && visits_)) &&
-                                               static_cast<long>(cu.size()) - nck0 <= kFlatMaxChunks ? 1 : 0);
-        };
-        const std::vector<int>& kp = plan_.kslot_ptr;
-        ck_wide_.clear();
-        ck_kind_.clear();
-        for (int l = 0; l < plan_.nlevels; l++) {
-            if (l == 0) { ck_wide_.push_back(false); ck_kind_.push_back(0); }
-            else if (visits_)
-                group(plan_.unit_level_ptr[l], plan_.unit_level_ptr[l + 1], [&](int u) { return late_b[u]; },
-                      [&](int u) { return kptr_v[u + 1]; }, &vis[l]);
-            else
-                group(plan_.unit_level_ptr[l], plan_.unit_level_ptr[l + 1], [&](int u) { return kp[u]; },
-                      [&](int u) { return kp[u + 1]; }, nullptr);
-            ck_ptr_[l + 1] = static_cast<int>(cu.size());
-            sp_ptr_[l + 1] = static_cast<int>(su.size());
-        }
-        const std::vector<int>& tp = plan_.tail_kslot_ptr;
-        if (plan_.nt > 0)
-            group(0, plan_.ntb * (plan_.ntb + 1) / 2, [&](int u) { return tp[u]; }, [&](int u) { return tp[u + 1]; },
-                  nullptr);
-        else { ck_wide_.push_back(false); ck_kind_.push_back(0); }
-        ck_ptr_[plan_.nlevels + 1] = static_cast<int>(cu.size());
-        sp_ptr_[plan_.nlevels + 1] = static_cast<int>(su.size());
-        dck_u_.upload(cu, s);
-        dck_b_.upload(cb, s);
-        dck_e_.upload(ce, s);
-        dck_part_.upload(cp, s);
-        dsp_u_.upload(su, s);
-        dsp_p0_.upload(sp0, s);
-        dsp_n_.upload(sn, s);
-        dck_q_.upload(cq, s);
-        dSplitCnt_.alloc(std::max<size_t>(1, su.size()));
-        IPO_HIP_CHECK(hipMemsetAsync(dSplitCnt_.get(), 0, std::max<size_t>(1, su.size()) * sizeof(int), s));
-        dPartialTile_.alloc(std::max<size_t>(1, max_part) * (kTileRows * kTileRows + 4 * kTileRows));
+        dst.upload(v, s);
         IPO_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    mark("launches per sweep and algor");
-    {   // launches per sweep and algorithmic work per phase occurrence
-        fwd_launches_ = bwd_launches_ = sf_level_ < plan_.nlevels ? 1 : 0;
-        for (int l = 0; l < sf_level_; l++) {
-            const int nsl = plan_.level_ptr[l + 1] - plan_.level_ptr[l];
-            const int nl = leaf_cnt_[l], n8 = leaf8_cnt_[l];
-            const int k = chunk_ptr_[l + 1] > chunk_ptr_[l] ? 2
-                        : (n8 > 0) + (nl > n8 && nsl > nl && merge_levels_ ? 1 : (nl > n8) + (nsl > nl));
-            fwd_launches_ += k;
-            bwd_launches_ += k;
-        }
-        if (plan_.nt > 0) {
-            const int chain = plan_.ntb <= kChainMaxBlocks;
-            fwd_launches_ += 1 + (chain ? 1 : plan_.ntb);
-            bwd_launches_ += chain ? 1 : 1 + plan_.ntb;
-        }
-        const auto& P = plan_;
-        double gf = 0, gb = 0;
-        auto tasks_work = [&](const std::vector<TailTask>& ts) {
-            for (const TailTask& t : ts) {
-                const double ncd = P.col0[t.src + 1] - P.col0[t.src];
-                const double nr = __builtin_popcountll(t.rmask), ncl = __builtin_popcountll(t.cmask);
-                gf += 2.0 * ncd * nr * ncl;
-                gb += 8.0 * ncd * (nr + ncl);
-            }
-        };
-        tasks_work(P.utasks);
-        tasks_work(P.tail_tasks);
-        double df = 0, db = 0, tf = 0, tb = 0, sf = 0, sb = 0, lxs = 0;
-        for (int sp = 0; sp < P.nsup; sp++) {
-            const double nc = P.col0[sp + 1] - P.col0[sp], hb = P.rowptr[sp + 1] - P.rowptr[sp];
-            df += 2.0 * nc * nc * nc / 3.0;
-            db += 8.0 * 1.5 * nc * nc;
-            tf += hb * nc * nc;
-            tb += 16.0 * hb * nc;
-            lxs += (nc + hb) * nc;
-            gb += 16.0 * (nc + hb) * nc;      // read-modify-write of every target panel
-        }
-        const double sdf = df, sdb = db, stf = tf, stb = tb;     // sparse panels alone
-        for (int kb = 0; kb < P.ntb; kb++) {
-            const double nc = std::min(kPanelCols, P.nt - kb * kPanelCols), below = P.nt - kb * kPanelCols - nc;
-            df += 2.0 * nc * nc * nc / 3.0;
-            db += 8.0 * 1.5 * nc * nc;
-            tf += below * nc * nc;
-            tb += 16.0 * below * nc;                                // L21 read + write
-            const double nb = P.ntb - kb - 1;
-            sf += 2.0 * nc * (nb * (nb + 1) / 2) * kTileRows * kTileRows;
-            sb += (nb * (nb + 1) / 2) * (16.0 * kTileRows * kTileRows + 16.0 * kTileRows * nc);
-        }
-        gb += 16.0 * 0.5 * P.nt * P.nt;                                 // tail block read-modify-write
-        work_flops[kPhGather] = gf; work_bytes[kPhGather] = gb;
-        work_flops[kPhDiag] = df; work_bytes[kPhDiag] = db;
-        work_flops[kPhTrsm] = tf; work_bytes[kPhTrsm] = tb;
-        work_flops[kPhSyrk] = sf; work_bytes[kPhSyrk] = sb;
-        // Algorithmic flops per factorisation in SURVEY.md 8(d)'s unit: the
-        // reference's narth (ldlt.c:1243-1248), split by the phase doing each
-        // column's work (kkt_plan.h: narth_tail / narth_gather / narth_panel,
-        // which sum to narth).  What the kernels execute (plan flops above,
-        // the dense tail's explicit zeros) is not the work.  Bytes: each
-        // phase's entries of L read and written once (+ the gather's source
-        // reads from the plan).
-        (void)sdf; (void)stf; (void)df; (void)tf; (void)sf; (void)lxs;
-        work_flops[kPhGather] = P.narth_gather;
-        if (use_panel_) {   // k_panel_w does both: the diag phase carries the sparse trsm work;
-            // the dense tail is its own phase (k_tail_pr: panels + deferred
-            // trailing updates; its repair launches)
-            work_flops[kPhDiag] = P.narth_panel; work_bytes[kPhDiag] = sdb + stb;
-            work_flops[kPhTrsm] = work_bytes[kPhTrsm] = 0;
-            work_flops[kPhSyrk] = work_bytes[kPhSyrk] = 0;
-            work_flops[kPhTail] = P.narth_tail;
-            work_bytes[kPhTail] = 16.0 * (static_cast<double>(P.lnz_tail) + P.nt);
-        } else {            // per-phase path: the tail's work goes with its trailing updates
-            work_flops[kPhDiag] = P.narth_panel;
-            work_flops[kPhTrsm] = 0;
-            work_flops[kPhSyrk] = P.narth_tail;
-        }
-        // a sweep (s (4 nnz(L) + N) per iteration, a solve
-        // being one forward and one backward sweep): 2 nnz(L) + N / 2 flops,
-        // every entry of L read once (12 B with its index) and the vector
-        // values in and out
-        for (int ph : {kPhForward, kPhBackward}) {
-            work_flops[ph] = 2.0 * static_cast<double>(P.lnz) + 0.5 * T_;
-            work_bytes[ph] = 12.0 * static_cast<double>(P.lnz) + 16.0 * T_;
-        }
-    }
-    mark("per-task source descriptors ");
-    {   // per-task source descriptors for the gather
-        auto build = [&](const std::vector<TailTask>& ts, DevBuf<TaskSrc>& dst) {
-            std::vector<TaskSrc> v(ts.size());
-            for (size_t t = 0; t < ts.size(); t++) {
-                const int d = ts[t].src, ncd = plan_.col0[d + 1] - plan_.col0[d];
-                v[t].colbase = plan_.off[d] + ncd;
-                v[t].hd = ncd + (plan_.rowptr[d + 1] - plan_.rowptr[d]);
-                v[t].cd0 = plan_.col0[d];
-            }
-            dst.upload(v, s);
-            IPO_HIP_CHECK(hipStreamSynchronize(s));
-        };
-        build(plan_.utasks, dusrc_);
-        if (plan_.nt > 0) build(plan_.tail_tasks, dtsrc_);
-        // per k-slot records of the gather (SlotRec), expanded from the
-        // slot -> task -> source panel indirection
-        auto expand = [&](const std::vector<int>& kslot, const std::vector<TailTask>& ts, DevBuf<SlotRec>& dst) {
-            std::vector<SlotRec> v(kslot.size());
-            for (size_t i = 0; i < kslot.size(); i++) {
-                const int sl = kslot[i];
-                SlotRec& r = v[i];
-                if (sl < 0) { r.rmask = r.cmask = 0; r.roff = 0; r.cdelta = 0; r.dk = 0; continue; }
-                const TailTask& t = ts[sl >> 6];
-                const int kl = sl & 63, d = t.src, ncd = plan_.col0[d + 1] - plan_.col0[d];
-                const int64_t hd = ncd + (plan_.rowptr[d + 1] - plan_.rowptr[d]);
-                r.rmask = t.rmask;
-                r.cmask = t.cmask;
-                r.roff = plan_.off[d] + ncd + kl * hd + t.rbase;
-                r.cdelta = t.cbase - t.rbase;
-                r.dk = plan_.col0[d] + kl;
-            }
-            dst.upload(v, s);
-            IPO_HIP_CHECK(hipStreamSynchronize(s));
-        };
-        expand(visits_ ? kslot_v : plan_.kslot, plan_.utasks, dslot_rec_);
-        if (plan_.nt > 0) expand(plan_.tail_kslot, plan_.tail_tasks, dtail_slot_rec_);
-    }
-    mark("dutasks_.upload(reinterpret_");
+    };
+    expand(visits_ ? kslot_v : plan_.kslot, plan_.utasks, dslot_rec_);
+    if (plan_.nt > 0) expand(plan_.tail_kslot, plan_.tail_tasks, dtail_slot_rec_);
     dutasks_.upload(reinterpret_cast<const uint64_t*>(plan_.utasks.data()), plan_.utasks.size() * 4, s);
+}
+
+// The dense tail: its task and slot lists, workspaces, the sweep chains'
+// LDS attributes, the visit schedule and the persistent run's items and
+// counters (cus: the device's CU count, one workgroup per CU per launch)
+void KktDevice::setup_tail(int cus) {
+    hipStream_t s = stream_;
     if (plan_.nt > 0) {
         dtail_task_ptr_.upload(plan_.tail_task_ptr, s);
         dtail_kslot_.upload(plan_.tail_kslot, s);
@@ -3600,50 +3642,31 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
             for (const void* f : {reinterpret_cast<const void*>(&k_tail_bwd_pair<1>),
                                   reinterpret_cast<const void*>(&k_tail_bwd_pair<2>)})
                 IPO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kPairBwdLds));
-            // two 64-row blocks per chain workgroup (IPO_HIP_CHAIN_PAIRS=1; default: one)
-            const char* cp = std::getenv("IPO_HIP_CHAIN_PAIRS");
-            chain_pairs_ = cp && std::atoi(cp) != 0;
             for (const void* f : {reinterpret_cast<const void*>(&k_tail_fwd_lead<1>),
                                   reinterpret_cast<const void*>(&k_tail_fwd_lead<2>)})
                 IPO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kChainLds));
-            // the forward sweep by a lead workgroup (default; IPO_HIP_CHAIN_LEAD=0: the per-block chain)
-            const char* cl = std::getenv("IPO_HIP_CHAIN_LEAD");
-            chain_lead_ = !(cl && std::atoi(cl) == 0);
         }
     }
-    if (const char* vb = std::getenv("IPO_HIP_VISIT_BLOCKS")) visit_blocks_ = std::max(1, std::atoi(vb));
     if (plan_.nt > 0 && plan_.ntb <= kTailSchedMaxBlocks) {
         // look-ahead launches of at most one workgroup per CU (tail_visit_schedule)
-        const char* vs = std::getenv("IPO_HIP_VISIT_SCHED");
-        if (!vs || std::atoi(vs) != 0) {
-            int dev = 0, cus = 0;
-            IPO_HIP_CHECK(hipGetDevice(&dev));
-            IPO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-            const std::vector<unsigned> vl = tail_visit_schedule(plan_.ntb, plan_.nt, visit_blocks_, cus, visit_ptr_);
+        if (knobs_.visit_sched) {
+            const std::vector<unsigned> vl =
+                tail_visit_schedule(plan_.ntb, plan_.nt, knobs_.visit_blocks, cus, knobs_.visit_xcd, visit_ptr_);
             dvisit_list_.upload(vl, s);
             IPO_HIP_CHECK(hipStreamSynchronize(s));   // vl is a local
         }
         // the persistent run (k_tail_run, default; its bails end in the same
         // state as the per-step launches', so the repair and the sharded
         // solve's per-phase redo are unchanged); the latest chunk of each
-        // column IPO_HIP_VISIT_LATEST blocks
-        const char* tr = std::getenv("IPO_HIP_TAIL_RUN");
-        tail_run_ = !(tr && std::atoi(tr) == 0);
+        // column knobs_.visit_latest blocks
         if (tail_run_) {
-            int dev = 0, cus = 0;
-            IPO_HIP_CHECK(hipGetDevice(&dev));
-            IPO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-            const char* vl = std::getenv("IPO_HIP_VISIT_LATEST");
-            const int latest = vl ? std::max(1, std::atoi(vl)) : kTailVisitLatest;
             const std::vector<uint2> items =
-                tail_run_schedule(plan_.ntb, plan_.nt, visit_blocks_, latest, cus, run_ptr_);
+                tail_run_schedule(plan_.ntb, plan_.nt, knobs_.visit_blocks, knobs_.visit_latest, cus, run_ptr_);
             drun_items_.upload(items, s);
             drun_cnt_.alloc(1 + plan_.ntb + static_cast<size_t>(plan_.ntb) * plan_.ntb + plan_.ntb);
             // each step's tile windows handed to the next step's pre-update as
-            // they complete (kkt_dense.hip RunPub; IPO_HIP_TAIL_WINPUB=0: the
-            // pre-update waits for the whole previous step and reads S)
-            const char* wp = std::getenv("IPO_HIP_TAIL_WINPUB");
-            run_winpub_ = !(wp && std::atoi(wp) == 0);
+            // they complete (kkt_dense.hip RunPub; off: the pre-update waits
+            // for the whole previous step and reads S)
             if (run_winpub_) {
                 drun_pub_.alloc(2 * static_cast<size_t>(plan_.ntb) * 4 * kTailPubWin);
                 drun_wflag_.alloc(static_cast<size_t>(plan_.ntb) * plan_.ntb * 4);
@@ -3653,16 +3676,15 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
             IPO_HIP_CHECK(hipStreamSynchronize(s));   // items is a local
         }
     }
-    if (const char* ts = std::getenv("IPO_HIP_TAIL_SPEC")) tail_spec_ = std::atoi(ts);
-    if (const char* sd = std::getenv("IPO_HIP_SPARSE_DEP")) sparse_dep_ = std::atoi(sd);
-    if (const char* em = std::getenv("IPO_HIP_EPSDIAG_MAX")) epsdiag_cap_ = std::atof(em);
+}
 
-    mark("dLx_.alloc(plan_.lx_size > 0");
+// The factor, its pivots and flags, the solve's vectors and scalars, events
+void KktDevice::alloc_numeric() {
+    hipStream_t s = stream_;
     dLx_.alloc(plan_.lx_size > 0 ? plan_.lx_size : 1);
     dDg_.alloc(T_ > 0 ? T_ : 1);
     dLive_.alloc(T_ > 0 ? T_ : 1);
     dDscale_.alloc(T_ > 0 ? T_ : 1);
-    if (const char* e = std::getenv("IPO_HIP_PIVTOL")) pivot_tol_ = std::atof(e);
     // flags: [0] ndep, [1] fused panel bail-out bits, [2] 1 + the dense-tail
     // block column whose look-ahead panel bailed, [4..4+T) node class sign
     dFlags_.alloc(4 + T_);
@@ -3672,10 +3694,10 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
         dFlags_.upload(fl, s);
     }
     dZ_.alloc(2 * (T_ > 0 ? T_ : 1));
-    dDy_.alloc(2 * (m > 0 ? m : 1));
-    dRy_.alloc(2 * (m > 0 ? m : 1));
-    dDx_.alloc(2 * (n > 0 ? n : 1));
-    dRx_.alloc(2 * (n > 0 ? n : 1));
+    dDy_.alloc(2 * (m_ > 0 ? m_ : 1));
+    dRy_.alloc(2 * (m_ > 0 ? m_ : 1));
+    dDx_.alloc(2 * (n_ > 0 ? n_ : 1));
+    dRx_.alloc(2 * (n_ > 0 ? n_ : 1));
     dIncons_.alloc(2);
     dPart_.alloc(8 * kRedBlocks);
     dScal_.alloc(16);
@@ -3686,7 +3708,6 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
     IPO_HIP_CHECK(hipEventCreate(&ev2_));
     IPO_HIP_CHECK(hipEventCreate(&ev3_));
     IPO_HIP_CHECK(hipStreamSynchronize(s));
-    mark("done");
 }
 
 // Sync-free top levels (k_fwd_sf / k_bwd_sf): from sf_level_ up every level
@@ -3699,18 +3720,19 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
 // large chunked supernodes, which the per-level launches spread wider).  Their forward update values get
 // ybuf slices, and their z values zpad slices, of their own 128-B lines;
 // work items, per-supernode arrival counts and parents.  Called from the
-// constructor after the solve chunks are built.
-void KktDevice::build_sync_free_plan() {
-    int kSfWidth = plan_.lx_size < (int64_t(1) << 25) ? 300 : 64;
-    if (const char* e = std::getenv("IPO_HIP_SF_WIDTH")) kSfWidth = std::max(1, std::atoi(e));
+// constructor after the solve chunks are built; also uploads the forward
+// update lists (yrow_ptr as the plan's, yrow_idx with the moved slices).
+// cus: the device's CU count, the sweeps' grid.
+void KktDevice::build_sync_free_plan(int cus) {
+    const int kSfWidth = knobs_.sf_width > 0 ? knobs_.sf_width : plan_.lx_size < (int64_t(1) << 25) ? 300 : 64;
     hipStream_t s = stream_;
+    dyrow_ptr_.upload(plan_.yrow_ptr, s);
     const KktPlan& P = plan_;
     const int ns = P.nsup;
     sf_level_ = P.nlevels;
     while (sf_level_ > 0 && P.level_ptr[sf_level_] - P.level_ptr[sf_level_ - 1] <= kSfWidth) sf_level_--;
     if (P.nlevels - sf_level_ < 2) sf_level_ = P.nlevels;
-    if (const char* e = std::getenv("IPO_HIP_SF"))
-        if (std::atoi(e) == 0) sf_level_ = P.nlevels;
+    if (!knobs_.sf) sf_level_ = P.nlevels;
     auto chunked = [&](int sp) { const int l = P.level[sp]; return chunk_ptr_[l + 1] > chunk_ptr_[l]; };
     auto nchunks = [&](int sp) { return (P.rowptr[sp + 1] - P.rowptr[sp] + 63) / 64; };
     std::vector<int> ybase(ns + 1), zbase(ns, -1), zpi(T_ > 0 ? T_ : 1, -1), need(ns, 0), par(ns, -1);
@@ -3745,39 +3767,35 @@ void KktDevice::build_sync_free_plan() {
     // in list order), and the sync-free items sum only the values of
     // supernodes inside the range (their own lists, ylate_*).
     pre_cols_ = 0;
-    {
-        const char* ve = std::getenv("IPO_HIP_VISITS");
-        const bool deep = ve ? std::atoi(ve) != 0 : P.nlevels >= kVisitLevels;
-        if (deep && sf_level_ < P.nlevels) {
-            auto src_of = [&](int i) {        // the supernode whose row set holds R entry i
-                return static_cast<int>(std::upper_bound(P.rowptr.begin(), P.rowptr.end(), i) - P.rowptr.begin()) - 1;
-            };
-            std::vector<int> lptr(T_ + 1, 0), lidx, ecol, eptr{0}, eidx;
-            for (int v = 0; v < T_; v++) {
-                const int sv = v < P.tail_c0 ? P.sup_of[v] : -1;
-                const bool in_range = sv >= 0 && P.level[sv] >= sf_level_;
-                bool any_early = false;
-                // (columns outside the range keep empty late lists: only k_fwd_sf reads these)
-                for (int e = in_range ? P.yrow_ptr[v] : 0; e < (in_range ? P.yrow_ptr[v + 1] : 0); e++) {
-                    const bool early = P.level[src_of(P.yrow_idx[e])] < sf_level_;
-                    if (early) {
-                        if (!any_early) { ecol.push_back(v); any_early = true; }
-                        eidx.push_back(yidx[e]);
-                    } else {
-                        lidx.push_back(yidx[e]);
-                    }
+    if (visits_ && sf_level_ < P.nlevels) {
+        auto src_of = [&](int i) {        // the supernode whose row set holds R entry i
+            return static_cast<int>(std::upper_bound(P.rowptr.begin(), P.rowptr.end(), i) - P.rowptr.begin()) - 1;
+        };
+        std::vector<int> lptr(T_ + 1, 0), lidx, ecol, eptr{0}, eidx;
+        for (int v = 0; v < T_; v++) {
+            const int sv = v < P.tail_c0 ? P.sup_of[v] : -1;
+            const bool in_range = sv >= 0 && P.level[sv] >= sf_level_;
+            bool any_early = false;
+            // (columns outside the range keep empty late lists: only k_fwd_sf reads these)
+            for (int e = in_range ? P.yrow_ptr[v] : 0; e < (in_range ? P.yrow_ptr[v + 1] : 0); e++) {
+                const bool early = P.level[src_of(P.yrow_idx[e])] < sf_level_;
+                if (early) {
+                    if (!any_early) { ecol.push_back(v); any_early = true; }
+                    eidx.push_back(yidx[e]);
+                } else {
+                    lidx.push_back(yidx[e]);
                 }
-                if (any_early) eptr.push_back(static_cast<int>(eidx.size()));
-                lptr[v + 1] = static_cast<int>(lidx.size());
             }
-            pre_cols_ = static_cast<int>(ecol.size());
-            dylate_ptr_.upload(lptr, s);
-            dylate_idx_.upload(lidx.empty() ? std::vector<int>{0} : lidx, s);
-            dpre_col_.upload(ecol.empty() ? std::vector<int>{0} : ecol, s);
-            dpre_ptr_.upload(eptr, s);
-            dpre_idx_.upload(eidx.empty() ? std::vector<int>{0} : eidx, s);
-            IPO_HIP_CHECK(hipStreamSynchronize(s));
+            if (any_early) eptr.push_back(static_cast<int>(eidx.size()));
+            lptr[v + 1] = static_cast<int>(lidx.size());
         }
+        pre_cols_ = static_cast<int>(ecol.size());
+        dylate_ptr_.upload(lptr, s);
+        dylate_idx_.upload(lidx.empty() ? std::vector<int>{0} : lidx, s);
+        dpre_col_.upload(ecol.empty() ? std::vector<int>{0} : ecol, s);
+        dpre_ptr_.upload(eptr, s);
+        dpre_idx_.upload(eidx.empty() ? std::vector<int>{0} : eidx, s);
+        IPO_HIP_CHECK(hipStreamSynchronize(s));
     }
     ybuf_stride_ = std::max<size_t>(yend, 1);
     dYbuf_.alloc(2 * ybuf_stride_);
@@ -3813,9 +3831,7 @@ void KktDevice::build_sync_free_plan() {
         dsf_ticket_.alloc(2);
         IPO_HIP_CHECK(hipMemsetAsync(dsf_ticket_.get(), 0, 2 * sizeof(int), s));
         sf_ticket_next_[0] = sf_ticket_next_[1] = 0;
-        int dev = 0;
-        IPO_HIP_CHECK(hipGetDevice(&dev));
-        IPO_HIP_CHECK(hipDeviceGetAttribute(&sf_grid_, hipDeviceAttributeMultiprocessorCount, dev));
+        sf_grid_ = cus;
         for (const void* f : {reinterpret_cast<const void*>(&k_fwd_sf<1>), reinterpret_cast<const void*>(&k_fwd_sf<2>),
                               reinterpret_cast<const void*>(&k_bwd_sf<1>), reinterpret_cast<const void*>(&k_bwd_sf<2>)})
             IPO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kChainLds));
@@ -3827,7 +3843,7 @@ void KktDevice::build_sync_free_plan() {
 // Per-level summary of the last forward sync-free sweep's stamps (10 ns
 // ticks): items, mean wait / diag (gather + L11 solve) / rest / hand-off,
 // and when the level's last item finished.
-static void dump_sf_stamps(const std::vector<int2>& items, const KktPlan& P) {
+static void dump_sf_stamps(const std::vector<int2>& items, const KktPlan& P, const std::string& file) {
     std::vector<long long> st((size_t)(1 << 15) * 10);
     if (hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(g_sfst), st.size() * sizeof(long long)) != hipSuccess) return;
     const int n = std::min<int>(items.size(), 1 << 15);
@@ -3840,8 +3856,8 @@ static void dump_sf_stamps(const std::vector<int2>& items, const KktPlan& P) {
         a[0] += 1; a[1] += x[1] - x[0]; a[2] += x[2] - x[1]; a[3] += x[3] - x[2]; a[4] = std::max<double>(a[4], x[4] - t0);
         a[5] += x[4] - x[3];
     }
-    if (const char* f = std::getenv("IPO_SF_STAMPS_FILE")) {
-        if (FILE* fo = std::fopen(f, "w")) {
+    if (!file.empty()) {
+        if (FILE* fo = std::fopen(file.c_str(), "w")) {
             for (int i = 0; i < n; i++) {
                 const long long* x = &st[i * 10];
                 std::fprintf(fo, "%d %d %d %d %lld %lld %lld %lld %lld %lld %lld %lld %lld\n", items[i].x, items[i].y,
@@ -3860,9 +3876,9 @@ static void dump_sf_stamps(const std::vector<int2>& items, const KktPlan& P) {
 
 KktDevice::~KktDevice() {
 #ifdef IPO_SF_STAMPS
-    if (!h_sf_items_f_.empty()) dump_sf_stamps(h_sf_items_f_, plan_);
+    if (!h_sf_items_f_.empty()) dump_sf_stamps(h_sf_items_f_, plan_, knobs_.sf_stamps_file);
 #endif
-    if (std::getenv("IPO_HIP_DEBUG_REDO"))
+    if (knobs_.debug_redo)
         std::fprintf(stderr, "kkt: %ld factorisations, %ld redone; bails (unused) %ld, k_panel_w sparse %ld, tail %ld, "
                              "k_panel_s %ld; tail block columns repaired %ld in %ld rounds\n", tm_.factors,
                      tm_.panel_redos, tm_.redo_where[0], tm_.redo_where[1], tm_.redo_where[2], tm_.redo_where[3],
@@ -3895,14 +3911,10 @@ static PlanView make_view(const KktPlan&, const DevBuf<int>& col0, const DevBuf<
 #define IPO_VIEW() with_scale(make_view(plan_, dcol0_, drowptr_, drows_, doff_, dunit_sup_, dunit_tile_, dtask_ptr_, \
                              dtask_pair_, dtask_i0_, dtask_i1_, dupd_src_, dupd_r0_, dupd_r1_, drelptr_, drel_, \
                              dLx_, dDg_, dLive_, dFlags_), dDscale_.get(), pivot_tol_, dIncons_.get(), \
-                             dybase_.get())
+                             dybase_.get(), knobs_.update_xcd)
 
-static PlanView with_scale(PlanView v, double* dscale, double tau, int* incons, const int* ybase) {
-    static const int xcd = [] {
-        const char* e = std::getenv("IPO_HIP_UPDATE_XCD");     // launches of at least this many chunks (0: off)
-        return e ? std::max(0, std::atoi(e)) : 1024;
-    }();
-    v.xcd = xcd;
+static PlanView with_scale(PlanView v, double* dscale, double tau, int* incons, const int* ybase, int xcd) {
+    v.xcd = xcd;     // gather launches of at least this many chunks walk them XCD by XCD (0: off)
     v.dscale = dscale;
     v.tau = tau;
     v.incons = incons;
@@ -3919,18 +3931,17 @@ TailView KktDevice::tail_view() const {
     t.task_ptr = dtail_task_ptr_.get();
     t.tasks = reinterpret_cast<const TailTask*>(dtail_tasks_.get());
     t.W = dW_.get();
-    t.vk = visit_blocks_;
+    t.vk = knobs_.visit_blocks;
     if (!visit_ptr_.empty()) {
         t.vlist = dvisit_list_.get();
         t.vptr = visit_ptr_.data();
     }
     // dependent pivots in the look-ahead panel: its failed checks fall back on
     // the host repair, which the sharded solve does not use
-    const char* rp = std::getenv("IPO_HIP_TAIL_REPAIR");
-    t.dep = use_panel_ && !xch_ && (!rp || std::atoi(rp) != 0) ? tail_spec_ : 0;
+    t.dep = tail_repair() ? knobs_.tail_spec : 0;
     // in the sparse panels a failed check falls back on redoing the factor
     // from the assembly, on every shard alike (the bail flags are reduced)
-    t.sdep = sparse_dep_;
+    t.sdep = knobs_.sparse_dep;
     return t;
 }
 
@@ -3941,8 +3952,7 @@ TailView KktDevice::tail_view() const {
 // Layout: int32 m, n, T, ndep; f64 eps_in, eps_out; f64 E[m], D[n];
 // int32 perm[T]; int32 live[T]; f64 dg[T]; f64 dscale[T] (new order).
 void KktDevice::dump_factor(const double* dE, const double* dD, double eps_in) {
-    const char* dir = std::getenv("IPO_HIP_DUMP_DIR");
-    if (!dir) return;
+    if (knobs_.dump_dir.empty()) return;
     std::vector<double> E(m_), D(n_), dg(T_), dsc(T_);
     std::vector<int> live(T_);
     IPO_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -3953,7 +3963,7 @@ void KktDevice::dump_factor(const double* dE, const double* dD, double eps_in) {
     dDscale_.download(dsc.data(), T_, stream_);
     IPO_HIP_CHECK(hipStreamSynchronize(stream_));
     char path[4096];
-    std::snprintf(path, sizeof path, "%s/f%04d.bin", dir, dump_count_++);
+    std::snprintf(path, sizeof path, "%s/f%04d.bin", knobs_.dump_dir.c_str(), dump_count_++);
     FILE* f = std::fopen(path, "wb");
     if (!f) return;
     const int hdr[4] = {m_, n_, T_, ndep_};
@@ -3983,8 +3993,7 @@ void KktDevice::factor_core(const double* dE, const double* dD) {
     // kernels there, which own the dependent-pivot rule, and the tail again
     // by the look-ahead (its own bails repaired the same way) -- a per-phase
     // tail costs a single-workgroup partial substitution per block column
-    const char* rp = std::getenv("IPO_HIP_TAIL_REPAIR");
-    const bool repair = use_panel_ && !xch_ && (!rp || std::atoi(rp) != 0);
+    const bool repair = tail_repair();
     bool ok = factor_pass(dE, dD, use_panel_, use_panel_);
     if (!ok) {
         tm_.panel_redos++;
@@ -4004,7 +4013,7 @@ void KktDevice::factor_core(const double* dE, const double* dD) {
     if (-hScal_[0] < 1.0e-14) epsdiag_ *= 10;
     // developer diagnostics (IPO_HIP_EPSDIAG_MAX, tools/status_loss_probe.py):
     // a cap on the growth above, to measure what a stalled solve owes to it
-    if (epsdiag_cap_ > 0.0 && epsdiag_ > epsdiag_cap_) epsdiag_ = epsdiag_cap_;
+    if (knobs_.epsdiag_max > 0.0 && epsdiag_ > knobs_.epsdiag_max) epsdiag_ = knobs_.epsdiag_max;
 }
 
 // One numeric factorisation, the sparse levels by the fused kernels (fused)
@@ -4092,7 +4101,7 @@ void KktDevice::enqueue_levels(const PlanView& pv, const TailView& tv, bool fuse
         } else if (fused) {
             const int nsm = small_ptr_[l + 1] - small_ptr_[l], nfu = fu_ptr_[l + 1] - fu_ptr_[l];
             const int n1 = small1_cnt_[l];
-            if (merge_panels_ && nfu > 0 && nsm > n1) {
+            if (knobs_.merge_levels && nfu > 0 && nsm > n1) {
                 launch_panel_small(pv, dsmall_sups_.get(), small_ptr_[l], n1, tv.sdep, s, n1);
                 launch_panel_ws(pv, dfu_sup_.get(), dfu_j_.get(), fu_ptr_[l], nfu, tv, dsmall_sups_.get(),
                                 small_ptr_[l] + n1, nsm - n1, tv.sdep, s);
@@ -4290,10 +4299,7 @@ int KktDevice::launch_gather(const PlanView& pv, const TailView& tv, int tail, i
                            dsp_p0_.get(), dsp_n_.get(), dSplitCnt_.get(), stq);
         return 1;
     }
-    static const int occ = [] {
-        const char* e = std::getenv("IPO_HIP_UPDATE_OCC");
-        return e ? std::atoi(e) : 4;
-    }();
+    const int occ = knobs_.update_occ;
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(c1 - c0), dim3(NT), 0, s, pv, tv, tail, recs, dck_u_.get(), dck_b_.get(),
                            dck_e_.get(), dck_part_.get(), c0, dPartialTile_.get(), dck_q_.get(), dsp_p0_.get(),
@@ -4365,7 +4371,7 @@ void KktDevice::sweep(double* dz, const double* epsp) {
             if (n8 > 0)
                 hipLaunchKernelGGL(k_fwd_leaf8<R>, dim3(ceil_div(n8, NT / kSmallLeaf)), dim3(NT), 0, s, pv,
                                    dsweep_sups_.get(), q0, n8, dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
-            if (nl > n8 && q1 - q0 > nl && merge_levels_) {
+            if (nl > n8 && q1 - q0 > nl && knobs_.merge_levels) {
                 const int nlb = ceil_div(nl - n8, NT / 64);
                 hipLaunchKernelGGL(k_fwd_level<R>, dim3(nlb + q1 - q0 - nl), dim3(NT), 0, s, pv, dsweep_sups_.get(),
                                    q0 + n8, nl - n8, nlb, dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
@@ -4409,7 +4415,7 @@ void KktDevice::sweep(double* dz, const double* epsp) {
             hipLaunchKernelGGL(k_tail_fwd_lead<R>, dim3(grid), dim3(kLeadNT), kChainLds, s, pv, tv, V, epsp,
                                dChainGran_.get(), dChainGran_.get() + static_cast<size_t>(plan_.ntb) * 2 * 128,
                                ++chain_epoch_, dlead_ticket_.get(), tb);
-        } else if (chain_pairs_)
+        } else if (knobs_.chain_pairs)
             hipLaunchKernelGGL(k_tail_fwd_pair<R>, dim3((plan_.ntb + 1) / 2), dim3(NT), kPairFwdLds, s, pv, tv, V, epsp,
                                dChainGran_.get(), ++chain_epoch_);
         else
@@ -4432,7 +4438,7 @@ void KktDevice::sweep(double* dz, const double* epsp) {
     ph_begin(s);
     if (plan_.nt > 0) {
         const TailView tv = tail_view();
-        if (chain_pairs_)
+        if (knobs_.chain_pairs)
             hipLaunchKernelGGL(k_tail_bwd_pair<R>, dim3((plan_.ntb + 1) / 2), dim3(NT), kPairBwdLds, s, pv, tv, V, epsp,
                                dChainGran_.get(), ++chain_epoch_);
         else
@@ -4459,7 +4465,7 @@ void KktDevice::sweep(double* dz, const double* epsp) {
             if (n8 > 0)
                 hipLaunchKernelGGL(k_bwd_leaf8<R>, dim3(ceil_div(n8, NT / kSmallLeaf)), dim3(NT), 0, s, pv,
                                    dsweep_sups_.get(), q0, n8, V, epsp);
-            if (nl > n8 && q1 - q0 > nl && merge_levels_) {
+            if (nl > n8 && q1 - q0 > nl && knobs_.merge_levels) {
                 const int nlb = ceil_div(nl - n8, NT / 64);
                 hipLaunchKernelGGL(k_bwd_level<R>, dim3(nlb + q1 - q0 - nl), dim3(NT), 0, s, pv, dsweep_sups_.get(),
                                    q0 + n8, nl - n8, nlb, V, epsp);

@@ -107,8 +107,9 @@ int tail_visit_tiles(int ntb, int t, int K);
 // The visits of every look-ahead launch placed so that no launch needs more
 // than `cap` workgroups (one round on `cap` CUs): visit_hi's chunks, with
 // tiles' first chunks moved into earlier launches where a launch would
-// overflow.  Returns the list (TailView::vlist layout) and ptr[0..ntb].
-std::vector<unsigned> tail_visit_schedule(int ntb, int nt, int K, int cap, std::vector<int>& ptr);
+// overflow.  xcd: a column's visits grouped on one XCD within each launch.
+// Returns the list (TailView::vlist layout) and ptr[0..ntb].
+std::vector<unsigned> tail_visit_schedule(int ntb, int nt, int K, int cap, bool xcd, std::vector<int>& ptr);
 // Items per launch t (ptr[t] .. ptr[t + 1]): panel workgroups (j, t | chunks
 // of column t << 8 | 1 << 31), then visits (bi | c << 8 | b0 << 16 | b1 << 24,
 // t | chunk index << 8), column t + 1's first.  Column c's chunks: the latest

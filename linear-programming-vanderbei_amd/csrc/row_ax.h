@@ -6,19 +6,19 @@
 #include <vector>
 
 #include "hip_util.h"
+#include "kkt_knobs.h"
 
 namespace ipo {
 
 // A x by rows through jagged diagonals (bitwise sparse_dot's sums, see
-// k_rows_ax_jds) when x exceeds kAxSliceBytes: rows_ax_blocks(n) = the
-// column slices, one pass each (default 1; IPO_HIP_AX_BLOCKS overrides).  RowAxPlan holds A's
+// k_rows_ax_jds) when x exceeds kAxSliceBytes: KktKnobs::ax_blocks column
+// slices, one pass each (default 1).  RowAxPlan holds A's
 // entries by slice in jagged-diagonal order (built once, on the host, from
 // the CSC of A); launch() writes ax[m], one kernel per pass.
 constexpr long kAxSliceBytes = 2l << 20;
-int rows_ax_blocks(int n);
-// whether A x goes through a RowAxPlan: more than one slice, or
-// IPO_HIP_AX_JDS=1 (jagged diagonals over a single slice)
-bool rows_ax_sliced(int n);
+// whether A x goes through a RowAxPlan: KktKnobs::ax_jds when set, else more
+// than one slice or x (n entries) larger than kAxSliceBytes
+bool rows_ax_sliced(const KktKnobs& knobs, int n);
 class RowAxPlan {
   public:
     void build(int m, int n, const int* kA, const int* iA, const double* A, int npass, hipStream_t st);

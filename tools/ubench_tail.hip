@@ -52,7 +52,8 @@ int main(int argc, char** argv) {
     if (!vs || std::atoi(vs) != 0) {
         int cus = 0;
         CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
-        const std::vector<unsigned> vl = ipo::tail_visit_schedule(ntb, nt, tv.vk, cus, vptr);
+        const std::vector<unsigned> vl =
+            ipo::tail_visit_schedule(ntb, nt, tv.vk, cus, ipo::KktKnobs::from_env().visit_xcd, vptr);
         CK(hipMalloc(&dvl, vl.size() * sizeof(unsigned) + 4));
         CK(hipMemcpy(dvl, vl.data(), vl.size() * sizeof(unsigned), hipMemcpyHostToDevice));
         tv.vlist = dvl;
