@@ -92,8 +92,9 @@ typedef struct {
     long   tail_dep_rounds;  /* k_tail_dep launches of those repairs                  */
 } ipo_hip_stats;
 
-/* method: 0 = hsd, 1 = intpt, 2 = hsdls.  trace may be NULL (silent).  timing != 0
- * records per-phase HIP-event times. */
+/* method: 0 = hsd, 1 = intpt, 2 = hsdls (3 = qp: with an empty Q, see
+ * ipo_hip_solve_qp).  trace may be NULL (silent).  timing != 0 records
+ * per-phase HIP-event times. */
 int ipo_hip_solve(int method, int m, int n, int nz, const int *iA, const int *kA, const double *A,
                   const double *b, const double *c, double f, double *x, double *y, double *w, double *z,
                   FILE *trace, int max_iter, int timing, ipo_hip_stats *stats);
@@ -108,6 +109,34 @@ int  ipo_hip_ctx_run(ipo_hip_ctx *ctx, int method, int max_iter, FILE *trace, in
 void ipo_hip_ctx_download(ipo_hip_ctx *ctx, double *x, double *y, double *w, double *z);
 void ipo_hip_ctx_destroy(ipo_hip_ctx *ctx);
 double ipo_hip_ctx_setup_seconds(const ipo_hip_ctx *ctx);
+
+/* ---- quadratic programs (an extension: the reference has no QP loop) --------
+ * Solves  max c'x + f - x'Qx / 2  s.t.  Ax <= b, x >= 0  by intpt.c's
+ * primal-dual path following with Q carried through (method 3, "qp": the
+ * same start point, step rule, stopping tests, trace format and status
+ * codes as method 1; the dual residual is c - A'y + z - Qx, the objectives
+ * printed are c'x - x'Qx / 2 + f and b'y + x'Qx / 2 + f, and the Newton
+ * system carries D + Q on its x block -- DESIGN.md §10).  Q is n x n, full
+ * symmetric CSC (both triangles and the nonzero diagonal, rows strictly
+ * ascending in each column: the layout of ipo_hip_ldlt_set_q), checked; it
+ * must be positive semidefinite, which is NOT checked: a non-convex Q gives
+ * an unspecified status.  kQ == NULL: an empty Q (the LP, by the QP loop).
+ * One thread walks one column of Q serially: meant for sparse Q (a Q with
+ * columns of thousands of entries runs, slowly).  Returns as ipo_hip_solve;
+ * an invalid Q returns 7 (ipo_hip_last_error).  No sharding, no HSD for QPs. */
+int ipo_hip_solve_qp(int m, int n, int nz, const int *iA, const int *kA, const double *A, const double *b,
+                     const double *c, double f, const int *kQ, const int *iQ, const double *Q, double *x,
+                     double *y, double *w, double *z, FILE *trace, int max_iter, int timing,
+                     ipo_hip_stats *stats);
+/* A persistent context with Q: with a nonempty Q it runs with
+ * ipo_hip_ctx_run(ctx, 3, ...) only (methods 0-2 return 7 with an error
+ * text); _download / _destroy as usual.  Method 3 on a context without Q
+ * (ipo_hip_ctx_create, or an empty Q here) runs with an empty Q: the LP, by
+ * method 1's iteration; on a sharded context it returns 7.  NULL on error
+ * (ipo_hip_last_error). */
+ipo_hip_ctx *ipo_hip_ctx_create_qp(int m, int n, const int *kA, const int *iA, const double *A,
+                                   const double *b, const double *c, double f, const int *kQ, const int *iQ,
+                                   const double *Q);
 
 /* ---- block-angular sharding (not in the reference) --------
  * One process per GPU.  Rank k passes its LOCAL problem: the rows and
@@ -146,7 +175,10 @@ int ipo_hip_run_mps(const char *path, int method, FILE *out, int timing, ipo_hip
  * split_free_columns).  solfile != NULL: the reference's writesol report
  * (iolp.c:976-1045, main.c:54-56 writes it to <NAME>.out) for the original
  * problem, z as solver() returned it (the reference reads it after freeing
- * it, hsd.c:290-291). */
+ * it, hsd.c:290-291).
+ * method 3 (qp) solves the file's QP, QUADS included (ipo_hip_mps_load_qp;
+ * methods 0-2 ignore QUADS, as solvelp does); with IPO_HIP_SPLIT_FREE it is
+ * refused: 7 and an error text, nothing solved. */
 #define IPO_HIP_SPLIT_FREE 1
 int ipo_hip_run_mps_ex(const char *path, int method, int flags, const char *solfile, FILE *out, int timing,
                        ipo_hip_stats *stats);
@@ -171,6 +203,15 @@ int ipo_hip_write_sol(const char *path, int flags, const double *x, const double
  * column.  Pass kQ = NULL to query n and qnz (-1: no QUADS section).
  * Returns 0 or the reader's error number (36: QUADS columns out of order). */
 int ipo_hip_mps_quads(const char *path, int *n, int *qnz, int *kQ, int *iQ, double *Q);
+
+/* The QP an MPS file with QUADS states, in the form ipo_hip_solve_qp takes
+ * (what ipo_hip_run_mps with method 3 solves): ipo_hip_mps_load's rows with
+ * Q carried through the lower-bound shift (c + Q l, f + c'l + l'Q l / 2) and
+ * Q_s = Q for MIN, -Q for MAX.  NULL pointers query the sizes first; kQ has
+ * n + 1 entries, qnz = 0 for a file without QUADS.  Host code.  Returns 0, 3
+ * (free variable) or the reader's error number. */
+int ipo_hip_mps_load_qp(const char *path, int *m, int *n, int *nz, int *kA, int *iA, double *A, double *b,
+                        double *c, double *f, int *qnz, int *kQ, int *iQ, double *Q);
 
 /* ipo_hip_mps_load with the flags of ipo_hip_run_mps_ex. */
 int ipo_hip_mps_load_ex(const char *path, int flags, int *m, int *n, int *nz, int *kA, int *iA, double *A,

@@ -40,7 +40,7 @@ ipo::Method method_from_env() {
 }
 
 ipo::Method method_from_int(int m) {
-    return m == 1 ? ipo::Method::Intpt : m == 2 ? ipo::Method::Hsdls : ipo::Method::Hsd;
+    return m == 1 ? ipo::Method::Intpt : m == 2 ? ipo::Method::Hsdls : m == 3 ? ipo::Method::Qp : ipo::Method::Hsd;
 }
 
 // MAX_ITER of each method: hsd.c:25, intpt.c:31, hsdls.c:25
@@ -113,13 +113,17 @@ void fill_stats(ipo_hip_stats* st, const ipo::IpmResult& r, const ipo::KktDevice
     }
 }
 
+void validate_q(int n, const int* kQ, const int* iQ, const double* Q);
+
 int solve_impl(ipo::Method method, int m, int n, int nz, const int* iA, const int* kA, const double* A,
                const double* b, const double* c, double f, double* x, double* y, double* w, double* z, FILE* trace,
-               int max_iter, int timing, ipo_hip_stats* stats, bool* dev_err = nullptr) {
+               int max_iter, int timing, ipo_hip_stats* stats, bool* dev_err = nullptr,
+               const ipo::QBlock* q = nullptr) {
     if (dev_err) *dev_err = false;
     try {
+        if (q && q->kQ) validate_q(n, q->kQ, q->iQ, q->Q);
         if (method != ipo::Method::Hsdls) print_small(trace, m, n, kA, iA, A, b, c);   // hsdls.c has no echo
-        ipo::IpmSolver S(m, n, kA, iA, A, b, c, f);
+        ipo::IpmSolver S(m, n, kA, iA, A, b, c, f, nullptr, nullptr, q);
         ipo::IpmOptions opt;
         opt.method = method;
         opt.trace = trace;
@@ -215,6 +219,30 @@ int ipo_hip_solve(int method, int m, int n, int nz, const int* iA, const int* kA
                   int timing, ipo_hip_stats* stats) {
     return solve_impl(method_from_int(method), m, n, nz, iA, kA, A, b, c, f, x, y, w, z,
                       trace, max_iter, timing, stats);
+}
+
+int ipo_hip_solve_qp(int m, int n, int nz, const int* iA, const int* kA, const double* A, const double* b,
+                     const double* c, double f, const int* kQ, const int* iQ, const double* Q, double* x, double* y,
+                     double* w, double* z, FILE* trace, int max_iter, int timing, ipo_hip_stats* stats) {
+    ipo::QBlock qb;
+    qb.kQ = kQ; qb.iQ = iQ; qb.Q = Q;
+    return solve_impl(ipo::Method::Qp, m, n, nz, iA, kA, A, b, c, f, x, y, w, z, trace, max_iter, timing, stats, nullptr,
+                      &qb);
+}
+
+ipo_hip_ctx* ipo_hip_ctx_create_qp(int m, int n, const int* kA, const int* iA, const double* A, const double* b,
+                                   const double* c, double f, const int* kQ, const int* iQ, const double* Q) {
+    try {
+        if (kQ) validate_q(n, kQ, iQ, Q);
+        ipo::QBlock qb;
+        qb.kQ = kQ; qb.iQ = iQ; qb.Q = Q;
+        auto ctx = std::make_unique<ipo_hip_ctx>();
+        ctx->solver = std::make_unique<ipo::IpmSolver>(m, n, kA, iA, A, b, c, f, nullptr, nullptr, &qb);
+        return ctx.release();
+    } catch (const std::exception& e) {
+        set_err(e.what());
+        return nullptr;
+    }
 }
 
 ipo_hip_ctx* ipo_hip_ctx_create(int m, int n, const int* kA, const int* iA, const double* A, const double* b,
@@ -317,7 +345,7 @@ namespace {
 // read + (optionally) split free columns + normalise; returns the
 // to_solver_form status (3: a free variable and no split requested)
 int load_form(const char* path, int flags, ipo::MpsProblem& p, ipo::MpsProblem& q, ipo::FreeMap& fm,
-              ipo::SolverForm& s, std::string& err, FILE* out) {
+              ipo::SolverForm& s, std::string& err, FILE* out, ipo::QpBlock* qs = nullptr) {
     const int rc = ipo::read_mps(path, p, &err);
     if (rc) return -rc;
     if (out) std::fprintf(out, "m = %d,n = %d,nz = %d \n", p.m, p.n, p.kA.empty() ? 0 : p.kA[p.n]);
@@ -325,6 +353,7 @@ int load_form(const char* path, int flags, ipo::MpsProblem& p, ipo::MpsProblem& 
         ipo::split_free_columns(p, q, fm);
         return ipo::to_solver_form(q, s);
     }
+    if (qs) return ipo::to_solver_form_qp(p, s, *qs);     // method qp: the file's QUADS carried along
     return ipo::to_solver_form(p, s);
 }
 }  // namespace
@@ -342,8 +371,17 @@ int ipo_hip_run_mps_ex(const char* path, int method, int flags, const char* solf
     ipo::MpsProblem p, q;
     ipo::FreeMap fm;
     ipo::SolverForm s;
+    ipo::QpBlock qs;
     std::string err;
-    int status = load_form(path, flags, p, q, fm, s, err, out);
+    const bool qp = method == 3;
+    if (qp && (flags & IPO_HIP_SPLIT_FREE)) {
+        // the split would need Q's rows and columns split with it: not built
+        set_err("method qp with IPO_HIP_SPLIT_FREE (split free columns) is not supported");
+        if (out) std::fprintf(out, "ERROR: %s\n\n", g_err.c_str());
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return 7;
+    }
+    int status = load_form(path, flags, p, q, fm, s, err, out, qp ? &qs : nullptr);
     if (status < 0) {
         set_err(err);
         if (out) std::fprintf(out, "ERROR(%d): %s\n\n", -status, err.c_str());
@@ -367,9 +405,11 @@ int ipo_hip_run_mps_ex(const char* path, int method, int flags, const char* solf
             for (int j = 0; j < s.n; j++) std::fprintf(out, "%10.5f \n", s.c[j]);
             std::fprintf(out, "\n");
         }
+        ipo::QBlock qb;
+        if (qp) { qb.kQ = qs.kQ.data(); qb.iQ = qs.iQ.data(); qb.Q = qs.Q.data(); }
         status = solve_impl(method_from_int(method), s.m, s.n, s.nz, s.iA.data(),
                             s.kA.data(), s.A.data(), s.b.data(), s.c.data(), s.f, x.data(), y.data(), w.data(),
-                            z.data(), out, 0, timing, stats, &dev_err);   // 0: the method's MAX_ITER
+                            z.data(), out, 0, timing, stats, &dev_err, qp ? &qb : nullptr);   // 0: the method's MAX_ITER
     }
     // a device / host exception is not a numerical outcome: no status text for it
     if (out) {
@@ -434,6 +474,33 @@ int ipo_hip_write_sol(const char* path, int flags, const double* x, const double
 int ipo_hip_mps_load(const char* path, int* m, int* n, int* nz, int* kA, int* iA, double* A, double* b, double* c,
                      double* f) {
     return ipo_hip_mps_load_ex(path, 0, m, n, nz, kA, iA, A, b, c, f);
+}
+
+int ipo_hip_mps_load_qp(const char* path, int* m, int* n, int* nz, int* kA, int* iA, double* A, double* b, double* c,
+                        double* f, int* qnz, int* kQ, int* iQ, double* Q) {
+    ipo::MpsProblem p;
+    ipo::SolverForm s;
+    ipo::QpBlock qs;
+    std::string err;
+    const int rc = ipo::read_mps(path, p, &err);
+    if (rc) { set_err(err); return rc; }
+    const int st = ipo::to_solver_form_qp(p, s, qs);
+    if (st) return st;
+    const int nq = qs.kQ[s.n];
+    if (m) *m = s.m;
+    if (n) *n = s.n;
+    if (nz) *nz = s.nz;
+    if (qnz) *qnz = nq;
+    if (kA) std::memcpy(kA, s.kA.data(), sizeof(int) * (s.n + 1));
+    if (iA) std::memcpy(iA, s.iA.data(), sizeof(int) * s.nz);
+    if (A) std::memcpy(A, s.A.data(), sizeof(double) * s.nz);
+    if (b) std::memcpy(b, s.b.data(), sizeof(double) * s.m);
+    if (c) std::memcpy(c, s.c.data(), sizeof(double) * s.n);
+    if (f) *f = s.f;
+    if (kQ) std::memcpy(kQ, qs.kQ.data(), sizeof(int) * (s.n + 1));
+    if (iQ && nq) std::memcpy(iQ, qs.iQ.data(), sizeof(int) * nq);
+    if (Q && nq) std::memcpy(Q, qs.Q.data(), sizeof(double) * nq);
+    return 0;
 }
 
 int ipo_hip_mps_load_ex(const char* path, int flags, int* m, int* n, int* nz, int* kA, int* iA, double* A, double* b,

@@ -3,6 +3,8 @@
 //   Method::Hsd    homogeneous self-dual predictor-corrector, src/ipo/hsd.c:27-311
 //   Method::Intpt  primal-dual path following,               src/ipo/intpt.c:33-261
 //   Method::Hsdls  homogeneous self-dual long step,          src/ipo/hsdls.c:38-296
+//   Method::Qp     intpt.c's path following with a quadratic objective term
+//                  (an extension: the reference has no QP loop)
 //
 // The host keeps the handful of scalars the reference keeps (phi, psi, mu,
 // theta, ...) and prints the reference's per-iteration trace; every O(m+n)
@@ -20,7 +22,7 @@
 
 namespace ipo {
 
-enum class Method { Hsd = 0, Intpt = 1, Hsdls = 2 };
+enum class Method { Hsd = 0, Intpt = 1, Hsdls = 2, Qp = 3 };
 
 struct IpmOptions {
     Method method = Method::Hsd;
@@ -62,9 +64,15 @@ void vector_bench(int m, int n, const int* kA, const int* iA, const double* A, i
 
 class IpmSolver {
   public:
+    // q: the QP's Q (n x n, full symmetric CSC, positive semidefinite; its
+    // qmax is not read): max c'x + f - x'Qx / 2.  With a nonempty Q the
+    // solver runs Method::Qp only, and cannot be sharded.
     IpmSolver(int m, int n, const int* kA, const int* iA, const double* A, const double* b, const double* c,
-              double f, hipStream_t stream = nullptr, const ShardSpec* shard = nullptr);
+              double f, hipStream_t stream = nullptr, const ShardSpec* shard = nullptr, const QBlock* q = nullptr);
     ~IpmSolver();
+    // Throws for an LP method on a solver built with a nonempty Q and for
+    // Method::Qp on a sharded solver.  Method::Qp without Q is the QP with an
+    // empty Q: the LP, on the LP's factor.
     int run(const IpmOptions& opt, IpmResult* res);
     // copy x (n), y (m), w (m), z (n) of the last run to the host
     void download(double* x, double* y, double* w, double* z) const;
@@ -75,6 +83,7 @@ class IpmSolver {
     int run_hsd(const IpmOptions& opt, IpmResult* res);
     int run_intpt(const IpmOptions& opt, IpmResult* res);
     int run_hsdls(const IpmOptions& opt, IpmResult* res);
+    int run_qp(const IpmOptions& opt, IpmResult* res);
     void reduce(const struct RedJobs& j, int nout);
     // sharded solve: linking-row products A_link x summed over the shards
     // into lax_ (no-op unsharded), and the cross-shard reduction of scalars
@@ -106,6 +115,10 @@ class IpmSolver {
     int dot_segmin_ = 0;         // RedJobs::segmin of the solver's dots (dev_common.h)
     long nzg_ = 0;
     std::unique_ptr<KktDevice> kkt_;
+    // a solver built with a nonempty Q: kkt_ is the factor with the roles of
+    // x and y swapped, so that Q sits on KktDevice's first block (run_qp)
+    bool has_q_ = false, sharded_ = false;
+    DevBuf<double> qx_;          // Q x (n)
     DevBuf<double> b_, c_, x_, y_, w_, z_;
     DevBuf<double> rho_, sig_, D_, E_, fx_, fy_, gx_, gy_, dx_, dy_, dz_, dw_;
     DevBuf<double> part_, part2_, scal_, lax_;

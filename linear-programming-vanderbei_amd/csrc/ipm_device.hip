@@ -22,6 +22,7 @@
 #include "dev_common.h"
 #include "hip_util.h"
 #include "ipm.h"
+#include "lp_io.h"
 
 namespace ipo {
 
@@ -295,6 +296,87 @@ k_pf_directions(int m, int n, double mu, const double* __restrict__ x, const dou
     if (threadIdx.x == 0) part[blockIdx.x] = th;
 }
 
+// ---------------------------------------------------------------- qp
+// k_pf_residuals with the quadratic term: for column j, (Q x)_j over Q's
+// column j (= its row j: Q is symmetric) in row order, kept in qx for the
+// objectives' x'Qx and subtracted last, sigma = ((c - A'y) + z) - Q x.  One
+// thread walks one column of Q serially (sparse Q).  Not sharded: no mcnt.
+__global__ void __launch_bounds__(kResThreads)
+k_qp_residuals(int m, int n, const int* __restrict__ kAt, const int* __restrict__ iAt, const double* __restrict__ At,
+               const int* __restrict__ kA, const int* __restrict__ iA, const double* __restrict__ A,
+               const int* __restrict__ kQ, const int* __restrict__ iQ, const double* __restrict__ Q,
+               const double* __restrict__ b, const double* __restrict__ c, const double* __restrict__ x,
+               const double* __restrict__ y, const double* __restrict__ w, const double* __restrict__ z,
+               double* __restrict__ rho, double* __restrict__ sig, double* __restrict__ qx, double* __restrict__ part,
+               int mrow, const double* __restrict__ lax) {
+    __shared__ double sh[kResThreads / 64];
+    double sr = 0.0, ss = 0.0;
+    for (int i = blockIdx.x * kResThreads + threadIdx.x; i < m + n; i += kRedBlocks * kResThreads) {
+        if (i < m) {
+            double ax = 0.0;
+            if (i >= mrow) ax = lax[i - mrow];      // A x formed column-blocked beforehand (row_ax)
+            else
+                ax = sparse_dot(kAt[i], kAt[i + 1], At, iAt, x);
+            const double r = b[i] - ax - w[i];
+            rho[i] = r;
+            sr += r * r;
+        } else {
+            const int j = i - m;
+            const double aty = sparse_dot(kA[j], kA[j + 1], A, iA, y);
+            const double q = sparse_dot(kQ[j], kQ[j + 1], Q, iQ, x);
+            const double s = ((c[j] - aty) + z[j]) - q;
+            qx[j] = q;
+            sig[j] = s;
+            ss += s * s;
+        }
+    }
+    sr = block_sum_w<kResThreads / 64>(sr, sh);
+    ss = block_sum_w<kResThreads / 64>(ss, sh);
+    if (threadIdx.x == 0) { part[blockIdx.x] = sr; part[kRedBlocks + blockIdx.x] = ss; }
+}
+
+// k_pf_rhs for the factor with the roles of x and y swapped (run_qp): the
+// same D, E and right-hand sides, the x block's negated -- the solve then
+// leaves dx in dx and -dy in dy
+__global__ void __launch_bounds__(NT)
+k_qp_rhs(int m, int n, double mu, const double* __restrict__ x, const double* __restrict__ z,
+         const double* __restrict__ y, const double* __restrict__ w, const double* __restrict__ rho,
+         const double* __restrict__ sig, double* __restrict__ D, double* __restrict__ E, double* __restrict__ dx,
+         double* __restrict__ dy) {
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i < n) { D[i] = z[i] / x[i]; dx[i] = -(sig[i] - z[i] + mu / x[i]); }
+    else if (i < n + m) { const int j = i - n; E[j] = w[j] / y[j]; dy[j] = rho[j] + w[j] - mu / y[j]; }
+}
+
+// k_pf_directions reading the swapped solve's dy (negated, and stored back
+// with its sign for k_step); dz = mu / x - z - D dx with D alone, not D + Q
+__global__ void __launch_bounds__(NT)
+k_qp_directions(int m, int n, double mu, const double* __restrict__ x, const double* __restrict__ z,
+                const double* __restrict__ y, const double* __restrict__ w, const double* __restrict__ D,
+                const double* __restrict__ E, const double* __restrict__ dx, double* __restrict__ dy,
+                double* __restrict__ dz, double* __restrict__ dw, double* __restrict__ part) {
+    __shared__ double sh[4];
+    double th = 0.0;
+    for (int i = blockIdx.x * NT + threadIdx.x; i < m + n; i += kRedBlocks * NT) {
+        if (i < n) {
+            const double v = mu / x[i] - z[i] - D[i] * dx[i];
+            dz[i] = v;
+            th = fmax(th, -dx[i] / x[i]);
+            th = fmax(th, -v / z[i]);
+        } else {
+            const int j = i - n;
+            const double ddy = -dy[j];
+            const double v = mu / y[j] - w[j] - E[j] * ddy;
+            dy[j] = ddy;
+            dw[j] = v;
+            th = fmax(th, -ddy / y[j]);
+            th = fmax(th, -v / w[j]);
+        }
+    }
+    th = block_max(th, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = th;
+}
+
 // host copy of ls_step for the (phi, psi) pair (hsdls.c:229)
 double ls_step_host(double xj, double zj, double dxj, double dzj, double beta, double delta, double mu) {
     const double a = dxj * dzj;
@@ -325,9 +407,12 @@ const char* kIntptHeader =
 }  // namespace
 
 IpmSolver::IpmSolver(int m, int n, const int* kA, const int* iA, const double* A, const double* b, const double* c,
-                     double f, hipStream_t stream, const ShardSpec* shard)
+                     double f, hipStream_t stream, const ShardSpec* shard, const QBlock* q)
     : m_(m), n_(n), f_(f), stream_(stream) {
     const double t0 = now_s();
+    sharded_ = shard != nullptr;
+    has_q_ = q && q->kQ && q->kQ[n] > 0;      // an empty Q is the LP: the LP's own factor
+    if (has_q_ && sharded_) throw std::invalid_argument("qp: a solver with Q cannot be sharded");
     mg_ = m;
     ng_ = n;
     nzg_ = kA[n];
@@ -350,9 +435,20 @@ IpmSolver::IpmSolver(int m, int n, const int* kA, const int* iA, const double* A
         IPO_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
         own_stream_ = true;
     }
-    kkt_ = std::make_unique<KktDevice>(m, n, kA, iA, A, stream_, nforced_);
-    kkt_->set_exchange(xch_);
-    if (dot_segmin_ > 0 && !xch_) {
+    if (has_q_) {
+        std::vector<int> kat, iat;
+        std::vector<double> at;
+        csc_transpose(m, n, kA, iA, A, kat, iat, at);
+        // KktDevice on A' (n x m): its first block, the one that takes a Q
+        // (kkt_device.h QBlock), is then the x block (run_qp)
+        QBlock qb = *q;
+        qb.qmax = 1;
+        kkt_ = std::make_unique<KktDevice>(n, m, kat.data(), iat.data(), at.data(), stream_, 0, &qb);
+    } else {
+        kkt_ = std::make_unique<KktDevice>(m, n, kA, iA, A, stream_, nforced_);
+        kkt_->set_exchange(xch_);
+    }
+    if (dot_segmin_ > 0 && !xch_ && !has_q_) {
         // trailing rows of at least kLongRow entries (the linking rows of a
         // block-angular LP): their serial row products held up the whole
         // refinement residual (1.5 ms a launch on configs[4])
@@ -366,7 +462,7 @@ IpmSolver::IpmSolver(int m, int n, const int* kA, const int* iA, const double* A
     const size_t mm = m > 0 ? m : 1, nn = n > 0 ? n : 1;
     b_.upload(b, m, stream_);
     c_.upload(c, n, stream_);
-    for (DevBuf<double>* v : {&x_, &z_, &sig_, &D_, &fx_, &gx_, &dx_, &dz_}) v->alloc(nn);
+    for (DevBuf<double>* v : {&x_, &z_, &sig_, &D_, &fx_, &gx_, &dx_, &dz_, &qx_}) v->alloc(nn);
     for (DevBuf<double>* v : {&y_, &w_, &rho_, &E_, &fy_, &gy_, &dy_, &dw_}) v->alloc(mm);
     if (m == 0) b_.alloc(1);
     if (n == 0) c_.alloc(1);
@@ -430,17 +526,23 @@ int IpmSolver::run(const IpmOptions& opt, IpmResult* res) {
     IpmResult local;
     if (!res) res = &local;
     *res = IpmResult();
+    const bool qp = opt.method == Method::Qp;
+    if (qp && sharded_) throw std::invalid_argument("qp: not supported on a sharded solver");
+    if (!qp && has_q_) throw std::invalid_argument("a solver built with Q runs method qp only (hsd, intpt and hsdls are LP methods)");
+    KktDevice& K = *kkt_;
     res->t_setup_s = t_setup_;
-    kkt_->enable_timing(opt.timing);
-    kkt_->reset_timers();         // the counters and phase times of this solve only
-    kkt_->set_epsdiag(1.0e-14);   // ldlt.c:31: every solve starts from the reference's eps_diag
+    K.enable_timing(opt.timing);
+    K.reset_timers();         // the counters and phase times of this solve only
+    K.set_epsdiag(1.0e-14);   // ldlt.c:31: every solve starts from the reference's eps_diag
     const double t0 = now_s();
-    const int st = opt.method == Method::Intpt   ? run_intpt(opt, res)
+    // an empty Q is the LP: intpt's iteration on the LP's factor
+    const int st = qp                            ? (has_q_ ? run_qp(opt, res) : run_intpt(opt, res))
+                   : opt.method == Method::Intpt ? run_intpt(opt, res)
                    : opt.method == Method::Hsdls ? run_hsdls(opt, res)
                                                  : run_hsd(opt, res);
     res->t_solve_s = now_s() - t0;
     res->status = st;
-    res->kkt = kkt_->timers();
+    res->kkt = K.timers();
     return st;
 }
 
@@ -757,6 +859,89 @@ int IpmSolver::run_intpt(const IpmOptions& opt, IpmResult* res) {
                            w_.get(), D_.get(), E_.get(), dx_.get(), dy_.get(), dz_.get(), dw_.get(), part_.get());
         hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 1, 1u, scal_.get());
         xsum(scal_.get(), 1, RedOp::Max);
+        IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), sizeof(double), hipMemcpyDeviceToHost, s));
+        IPO_HIP_CHECK(hipStreamSynchronize(s));
+        double theta = hs_[0];
+        theta = (r / theta > 1.0) ? 1.0 : r / theta;
+        hipLaunchKernelGGL(k_step, dim3(gv), dim3(NT), 0, s, m, n, theta, static_cast<const double*>(nullptr), x_.get(), dx_.get(), z_.get(), dz_.get(),
+                           y_.get(), dy_.get(), w_.get(), dw_.get());
+        normr0 = normr;
+        norms0 = norms;
+    }
+    IPO_HIP_CHECK(hipGetLastError());
+    IPO_HIP_CHECK(hipStreamSynchronize(s));
+    res->iters = iter;
+    return status;
+}
+
+// run_intpt with a quadratic objective term, max c'x + f - x'Qx / 2 (an
+// extension: the reference has no QP loop).  Same start, delta, r, stopping
+// and give-up tests, printed quantities and trace as run_intpt; sigma and
+// the objectives carry Q (k_qp_residuals), and the Newton system is
+//   -E dy + A dx = rho + w - mu / y,   A'dy + (D + Q) dx = sigma - z + mu / x.
+// The solver holds the factor of the swapped roles (KktDevice on A' with
+// E' = D, D' = E and Q on its first block), called with fy' = -fx,
+// fx' = fy and read back as dx = dy', dy = -dx' (k_qp_rhs, k_qp_directions);
+// its kA() is the CSR of A and its kAt() the CSC.  (Without Q the problem is
+// the LP and run() takes run_intpt.)
+int IpmSolver::run_qp(const IpmOptions& opt, IpmResult* res) {
+    const int m = m_, n = n_;
+    hipStream_t s = stream_;
+    const int gv = ceil_div(m + n, NT);
+    FILE* tr = opt.trace;
+    for (DevBuf<double>* v : {&x_, &z_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(n, NT)), dim3(NT), 0, s, n, 1000.0, v->get());
+    for (DevBuf<double>* v : {&y_, &w_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(m, NT)), dim3(NT), 0, s, m, 1000.0, v->get());
+    const double delta = 0.02, r = 0.9;
+    double normr0 = HUGE_VAL, norms0 = HUGE_VAL;
+    if (tr) {
+        print_dims(tr);
+        std::fputs(kIntptHeader, tr);
+        std::fflush(tr);
+    }
+    KktDevice& K = *kkt_;
+    int status = 5, iter;
+    for (iter = 0; iter < opt.max_iter; iter++) {
+        row_ax(x_.get(), s);
+        hipLaunchKernelGGL(k_qp_residuals, dim3(kRedBlocks), dim3(kResThreads), 0, s, m, n, K.kA(), K.iA(), K.A(), K.kAt(),
+                           K.iAt(), K.At(), K.kQ(), K.iQ(), K.Q(), b_.get(), c_.get(), x_.get(), y_.get(), w_.get(), z_.get(), rho_.get(),
+                           sig_.get(), qx_.get(), part_.get(), mrow(), lax());
+        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 2, 0u, scal_.get() + 8);
+        RedJobs j{};
+        j.nj = 5;
+        j.segmin = dot_segmin_;
+        j.a[0] = z_.get(); j.b[0] = x_.get(); j.len[0] = n; j.op[0] = 0;
+        j.a[1] = y_.get(); j.b[1] = w_.get(); j.len[1] = m; j.op[1] = 0;
+        j.a[2] = c_.get(); j.b[2] = x_.get(); j.len[2] = n; j.op[2] = 0;
+        j.a[3] = b_.get(); j.b[3] = y_.get(); j.len[3] = m; j.op[3] = 0;
+        j.a[4] = x_.get(); j.b[4] = qx_.get(); j.len[4] = n; j.op[4] = 0;     // x'Qx
+        launch_reduce(j, part_.get(), scal_.get(), s);
+        IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), 10 * sizeof(double), hipMemcpyDeviceToHost, s));
+        IPO_HIP_CHECK(hipStreamSynchronize(s));
+        // the printed quantities in single precision, as run_intpt (intpt.c:47)
+        const float normr = static_cast<float>(std::sqrt(hs_[8]));
+        const float norms = static_cast<float>(std::sqrt(hs_[9]));
+        const double gamma = hs_[0] + hs_[1];
+        const double hxqx = 0.5 * hs_[4];
+        const float pobj = static_cast<float>(hs_[2] - hxqx + f_);
+        const float dobj = static_cast<float>(hs_[3] + hxqx + f_);
+        if (tr) {
+            std::fprintf(tr, "%8d   %14.7e  %8.1e    %14.7e  %8.1e \n", iter, pobj, normr, dobj, norms);
+            std::fflush(tr);
+        }
+        res->final_mu = gamma; res->final_pobj = pobj; res->final_dobj = dobj;
+        res->final_pinf = normr; res->final_dinf = norms;
+        if (normr < 1.0e-6 && norms < 1.0e-6 && gamma < 1.0e-6) { status = 0; break; }
+        if (normr > 10 * normr0) { status = 2; break; }
+        if (norms > 10 * norms0) { status = 4; break; }
+        const double mu = delta * gamma / (n + m);
+        hipLaunchKernelGGL(k_qp_rhs, dim3(gv), dim3(NT), 0, s, m, n, mu, x_.get(), z_.get(), y_.get(), w_.get(),
+                           rho_.get(), sig_.get(), D_.get(), E_.get(), dx_.get(), dy_.get());
+        K.factor(D_.get(), E_.get());
+        K.solve(D_.get(), E_.get(), dx_.get(), dy_.get());
+        res->refine_passes += K.last_passes();
+        hipLaunchKernelGGL(k_qp_directions, dim3(kRedBlocks), dim3(NT), 0, s, m, n, mu, x_.get(), z_.get(), y_.get(),
+                           w_.get(), D_.get(), E_.get(), dx_.get(), dy_.get(), dz_.get(), dw_.get(), part_.get());
+        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 1, 1u, scal_.get());
         IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), sizeof(double), hipMemcpyDeviceToHost, s));
         IPO_HIP_CHECK(hipStreamSynchronize(s));
         double theta = hs_[0];

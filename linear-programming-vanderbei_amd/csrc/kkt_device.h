@@ -128,6 +128,10 @@ class KktDevice {
     const int* kAt() const { return dkAt_.get(); }
     const int* iAt() const { return diAt_.get(); }
     const double* At() const { return dAt_.get(); }
+    // Device copy of the Q block (CSC over the m y-nodes); null without entries.
+    const int* kQ() const { return qnz_ > 0 ? dkQ_.get() : nullptr; }
+    const int* iQ() const { return qnz_ > 0 ? diQ_.get() : nullptr; }
+    const double* Q() const { return qnz_ > 0 ? dQ_.get() : nullptr; }
 
     // Numeric factorisation of K(E, D); E (m), D (n) are device vectors.
     void factor(const double* dE, const double* dD);

@@ -545,4 +545,30 @@ int to_solver_form(const MpsProblem& p, SolverForm& s) {
     return 0;
 }
 
+int to_solver_form_qp(const MpsProblem& p, SolverForm& s, QpBlock& q) {
+    q = QpBlock();
+    const int st = to_solver_form(p, s);
+    if (st) return st;
+    const int n = p.n;
+    q.kQ.assign(n + 1, 0);
+    if (p.kQ.empty()) return 0;
+    // to_solver_form left c_s = -sense c and f_s = -sense (f + c'l); the
+    // shift's quadratic part joins them with the same sign: Q l and l'Q l / 2
+    const double sg = p.sense == 1 ? -1.0 : 1.0;
+    double lql = 0.0;
+    for (int j = 0; j < n; j++) {
+        double ql = 0.0;      // (Q l)_j over column j = row j of the symmetric Q
+        for (int k = p.kQ[j]; k < p.kQ[j + 1]; k++) ql += p.Q[k] * p.l[p.iQ[k]];
+        s.c[j] += sg * ql;
+        lql += p.l[j] * ql;
+    }
+    s.f += sg * (0.5 * lql);
+    q.kQ = p.kQ;
+    q.iQ = p.iQ;
+    q.Q = p.Q;
+    if (p.sense != 1)
+        for (double& v : q.Q) v *= -1;
+    return 0;
+}
+
 }  // namespace ipo

@@ -51,6 +51,21 @@ struct SolverForm {
 // Returns 0, or 3 ("dual unbounded") when a variable has no lower bound.
 int to_solver_form(const MpsProblem& p, SolverForm& s);
 
+// The QP normalisation (an extension: solvelp passes no Q to solver()).  The
+// MPS objective is sense (c'x + x'Qx / 2 + f) with QUADS as read_mps keeps
+// it; to_solver_form's transform with Q carried through the lower-bound
+// shift x = l + x' (c <- c + Q l, f <- f + c'l + l'Q l / 2, then the
+// negation for MIN) and Q_s = sense Q (sense 1 MIN, -1 MAX; the reference's
+// -max Q, ldlt.c:253-256), so that solver form reads
+//   max c_s'x' + f_s - x'Q_s x' / 2,  A_s x' <= b_s,  x' >= 0.
+// Rows, ranges, upper bounds and the column count are to_solver_form's.
+// kQ has n + 1 entries (all zero for a file without QUADS).
+struct QpBlock {
+    std::vector<int> kQ, iQ;
+    std::vector<double> Q;
+};
+int to_solver_form_qp(const MpsProblem& p, SolverForm& s, QpBlock& q);
+
 // Free-variable extension (not in the reference, which aborts with status
 // 3, solve.c:79-87): an equivalent problem whose
 // every column has a finite lower bound.

@@ -16,7 +16,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import tempfile
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -29,7 +29,7 @@ STATUS_TEXT = {
     4: "dual infeasible", 5: "iteration limit", 6: "infinite lower bounds - not implemented",
     7: "suboptimal solution",
 }
-METHODS = {"hsd": 0, "intpt": 1, "hsdls": 2}
+METHODS = {"hsd": 0, "intpt": 1, "hsdls": 2, "qp": 3}
 
 
 class IpoHipError(RuntimeError):
@@ -81,6 +81,7 @@ EXPORTED = [
     "ipo_hip_dot_ordered",
     "ipo_hip_kkt_create_q", "ipo_hip_ldlt_set_q", "ipo_hip_symbolic_q", "ipo_hip_mps_quads",
     "ipo_hip_symbolic_tail",
+    "ipo_hip_solve_qp", "ipo_hip_ctx_create_qp", "ipo_hip_mps_load_qp",
 ]
 
 # int (*)(void *user, double *buf, long n, int op)  -- ipo_hip_allreduce_fn
@@ -110,6 +111,14 @@ def lib() -> C.CDLL:
     L.inv_clo.restype = None
     L.ipo_hip_solve.argtypes = [_I, _I, _I, _I, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P, _I, _I, C.POINTER(Stats)]
     L.ipo_hip_solve.restype = _I
+    L.ipo_hip_solve_qp.argtypes = [_I, _I, _I, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I,
+                                   C.POINTER(Stats)]
+    L.ipo_hip_solve_qp.restype = _I
+    L.ipo_hip_ctx_create_qp.argtypes = [_I, _I, _P, _P, _P, _P, _P, _D, _P, _P, _P]
+    L.ipo_hip_ctx_create_qp.restype = _P
+    L.ipo_hip_mps_load_qp.argtypes = [C.c_char_p, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _P, _P, _P, _P, _P,
+                                      C.POINTER(_D), C.POINTER(_I), _P, _P, _P]
+    L.ipo_hip_mps_load_qp.restype = _I
     L.ipo_hip_run_mps.argtypes = [C.c_char_p, _I, _P, _I, C.POINTER(Stats)]
     L.ipo_hip_run_mps.restype = _I
     L.ipo_hip_run_mps_ex.argtypes = [C.c_char_p, _I, _I, C.c_char_p, _P, _I, C.POINTER(Stats)]
@@ -221,7 +230,9 @@ def require_gpu() -> None:
 # ----------------------------------------------------------------- MPS front end
 @dataclass
 class SolverForm:
-    """Problem in the form solver() takes: max c'x + f, Ax <= b, x >= 0 (A CSC)."""
+    """Problem in the form solver() takes: max c'x + f, Ax <= b, x >= 0 (A CSC).
+    q = (kQ, iQ, Q): a quadratic program, max c'x + f - x'Qx / 2 (Q n x n,
+    full symmetric CSC, positive semidefinite); method "qp" only."""
     m: int
     n: int
     kA: np.ndarray
@@ -230,6 +241,7 @@ class SolverForm:
     b: np.ndarray
     c: np.ndarray
     f: float
+    q: tuple = field(default=None, kw_only=True)     # keyword only: subclasses add positional fields
 
     @property
     def nz(self) -> int:
@@ -295,6 +307,41 @@ def load_mps(path: str, free: str = "abort") -> SolverForm:
     return SolverForm(m.value, n.value, kA, iA, A, b, c, f.value)
 
 
+def load_mps_qp(path: str) -> SolverForm:
+    """The quadratic program of an MPS file with QUADS in solver form (host
+    code; what run_mps(path, "qp") solves): load_mps's rows, the objective
+    with Q carried through the lower-bound shift, q = (kQ, iQ, Q_s) with
+    Q_s = Q for MIN and -Q for MAX (empty for a file without QUADS)."""
+    L = lib()
+    m, n, nz, qnz = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    st = L.ipo_hip_mps_load_qp(path.encode(), C.byref(m), C.byref(n), C.byref(nz), None, None, None, None, None, None,
+                               C.byref(qnz), None, None, None)
+    if st:
+        raise IpoHipError(f"mps load {path}: status {st} {last_error()}")
+    kA = np.zeros(n.value + 1, np.int32)
+    iA = np.zeros(nz.value, np.int32)
+    A = np.zeros(nz.value, np.float64)
+    b = np.zeros(m.value, np.float64)
+    c = np.zeros(n.value, np.float64)
+    f = C.c_double(0.0)
+    kQ = np.zeros(n.value + 1, np.int32)
+    iQ = np.zeros(max(qnz.value, 1), np.int32)
+    Q = np.zeros(max(qnz.value, 1), np.float64)
+    L.ipo_hip_mps_load_qp(path.encode(), C.byref(m), C.byref(n), C.byref(nz), _ptr(kA), _ptr(iA), _ptr(A), _ptr(b),
+                          _ptr(c), C.byref(f), C.byref(qnz), _ptr(kQ), _ptr(iQ), _ptr(Q))
+    return SolverForm(m.value, n.value, kA, iA, A, b, c, f.value, q=(kQ, iQ[:qnz.value], Q[:qnz.value]))
+
+
+def _q_arrays(q):
+    """(kQ, iQ, Q) contiguous for the C side (iQ / Q never zero-length buffers)."""
+    kQ = np.ascontiguousarray(q[0], np.int32)
+    iQ = np.ascontiguousarray(q[1], np.int32)
+    Q = np.ascontiguousarray(q[2], np.float64)
+    if iQ.size == 0:
+        iQ, Q = np.zeros(1, np.int32), np.zeros(1, np.float64)
+    return kQ, iQ, Q
+
+
 def write_sol(path: str, x, y, z, solfile: str, free: str = "abort") -> None:
     """writesol (iolp.c:976-1045) of MPS file `path` from solver()-form
     vectors of its normalisation (host code)."""
@@ -325,7 +372,8 @@ def _capture(fn):
 
 def run_mps(path: str, method: str = "hsd", timing: bool = False, free: str = "abort", solfile: str = None):
     """Equivalent of `ipo path` (main.c) on the GPU.  Returns (status, stdout text, stats dict).
-    free="split": the free-variable extension; solfile: write the writesol report there."""
+    free="split": the free-variable extension; solfile: write the writesol report there.
+    method="qp": the file's quadratic program, QUADS included (not with free="split")."""
     require_gpu()
     st = Stats()
     fl = SPLIT_FREE if free == "split" else 0
@@ -336,7 +384,9 @@ def run_mps(path: str, method: str = "hsd", timing: bool = False, free: str = "a
 
 
 def solver(p: SolverForm, method: str = "hsd", trace: bool = False, max_iter: int = 200, timing: bool = False):
-    """solver() on host arrays.  Returns dict(status, x, y, w, z, stats, trace)."""
+    """solver() on host arrays.  Returns dict(status, x, y, w, z, stats, trace).
+    method="qp": the quadratic program with p.q (ipo_hip_solve_qp; an empty Q
+    without it).  A problem with q takes no other method."""
     require_gpu()
     x = np.zeros(p.n, np.float64)
     z = np.zeros(p.n, np.float64)
@@ -349,7 +399,16 @@ def solver(p: SolverForm, method: str = "hsd", trace: bool = False, max_iter: in
     b = np.ascontiguousarray(p.b, np.float64)
     c = np.ascontiguousarray(p.c, np.float64)
 
+    q = getattr(p, "q", None)
+    if q is not None and method != "qp":
+        raise IpoHipError(f"solver: a problem with q takes method 'qp', not '{method}'")
+    qa = _q_arrays(q) if q is not None else None
+
     def call(fp):
+        if method == "qp":
+            return lib().ipo_hip_solve_qp(p.m, p.n, p.nz, _ptr(iA), _ptr(kA), _ptr(A), _ptr(b), _ptr(c), float(p.f),
+                                          *([_ptr(a) for a in qa] if qa else [None] * 3), _ptr(x), _ptr(y), _ptr(w),
+                                          _ptr(z), fp, max_iter, int(timing), C.byref(st))
         return lib().ipo_hip_solve(METHODS[method], p.m, p.n, p.nz, _ptr(iA), _ptr(kA), _ptr(A), _ptr(b), _ptr(c),
                                    float(p.f), _ptr(x), _ptr(y), _ptr(w), _ptr(z), fp, max_iter, int(timing),
                                    C.byref(st))
@@ -433,7 +492,9 @@ class KktFactor:
 
 
 class Context:
-    """Device-resident problem (ipo_hip_ctx): setup once, run() many times."""
+    """Device-resident problem (ipo_hip_ctx): setup once, run() many times.
+    A problem with q (SolverForm.q) gives a QP context (ipo_hip_ctx_create_qp),
+    which runs method "qp" only."""
 
     def __init__(self, p: SolverForm):
         require_gpu()
@@ -441,7 +502,13 @@ class Context:
         self._keep = [np.ascontiguousarray(p.kA, np.int32), np.ascontiguousarray(p.iA, np.int32),
                       np.ascontiguousarray(p.A, np.float64), np.ascontiguousarray(p.b, np.float64),
                       np.ascontiguousarray(p.c, np.float64)]
-        self.h = lib().ipo_hip_ctx_create(p.m, p.n, *[_ptr(a) for a in self._keep], float(p.f))
+        q = getattr(p, "q", None)
+        if q is not None:
+            qa = _q_arrays(q)
+            self.h = lib().ipo_hip_ctx_create_qp(p.m, p.n, *[_ptr(a) for a in self._keep], float(p.f),
+                                                 *[_ptr(a) for a in qa])
+        else:
+            self.h = lib().ipo_hip_ctx_create(p.m, p.n, *[_ptr(a) for a in self._keep], float(p.f))
         if not self.h:
             raise IpoHipError("ctx create: " + last_error())
         self.setup_seconds = lib().ipo_hip_ctx_setup_seconds(self.h)
