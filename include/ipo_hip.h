@@ -290,7 +290,7 @@ int ipo_hip_synth_block_angular(int nblocks, int mb, int nb, int per_col, int ba
                                 double *b, double *c, double *xs, double *ys, double *ws, double *zs);
 
 /* The persistent dense tail's work-item schedule (host-only; test entry, no
- * reference counterpart): k_tail_run's (kkt_dense.hip tail_run_schedule),
+ * reference counterpart): k_tail_run's (kkt_schedule.cpp tail_run_schedule),
  * for a tail of nt columns, visit chunks of K blocks, latest chunk L, at most
  * cap workgroups per launch.  nt may give at most 255 block columns (the
  * items pack block indices into 8 bits): more is an error.
@@ -301,6 +301,21 @@ int ipo_hip_synth_block_angular(int nblocks, int mb, int nb, int per_col, int ba
  * ipo_hip_tail_schedule with a leading `kind` argument; the new name keeps a
  * caller built for that argument list from binding to this one.) */
 int ipo_hip_tail_run_schedule(int nt, int K, int L, int cap, unsigned *items, int max_items, int *ptr);
+
+/* One integer array of the launch schedule a KktFactor of this pattern builds
+ * before it uploads anything (host-only; test entry, no reference
+ * counterpart, no HIP call): the plan as ipo_hip_symbolic_tail builds it
+ * (nforced: trailing linking rows), the runtime knobs from the environment,
+ * a device of `cus` compute units (kkt_schedule.h build_kkt_schedule).
+ * name: "<part>.<member>" of KktSchedule ("sf.items_f", "gather.ck_u", ...),
+ * "paths", "<part>.dims", or "plan.<member>" for the plan's own arrays;
+ * pairs and triples come out flattened.  Several names separated by commas
+ * give, for each in turn, its length followed by its entries (one build of
+ * the plan for a whole schedule).  Returns the length of what the name asks
+ * for (at most cap entries are written to out, which may be NULL), or -1 for
+ * an unknown name or an error (ipo_hip_last_error). */
+long ipo_hip_kkt_schedule(int m, int n, const int *kA, const int *iA, int nforced, int cus, const char *name, int *out,
+                          long cap);
 
 int ipo_hip_device_count(void);
 /* hipDeviceSynchronize on the calling thread's device (bench.py brackets its

@@ -10,17 +10,14 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "ipm.h"
 #include "kkt_device.h"
+#include "kkt_schedule.h"
 #include "lp_io.h"
 #include "synth.h"
-
-namespace ipo {
-// kkt_dense.hip (declared in kkt_kernels.h, which holds device code)
-std::vector<uint2> tail_run_schedule(int ntb, int nt, int K, int L, int cap, std::vector<int>& ptr);
-}  // namespace ipo
 
 namespace {
 
@@ -797,6 +794,76 @@ const char* ipo_hip_version(void) { return "ipo-hip 0.1 (gfx950)"; }
 }  // extern "C"
 
 namespace {
+// One integer array of a plan ("plan.<member>") or of its launch schedule
+// (part.member of KktSchedule), pairs and triples flattened
+// (ipo_hip_kkt_schedule).
+std::vector<int> schedule_array(const ipo::KktPlan& P, const ipo::KktSchedule& S, const std::string& name) {
+    using V = std::vector<int>;
+    const auto flat2 = [](const std::vector<ipo::SchedInt2>& w) {
+        V v;
+        for (const ipo::SchedInt2& e : w) { v.push_back(e.x); v.push_back(e.y); }
+        return v;
+    };
+    const auto chars = [](const std::vector<char>& w) { return V(w.begin(), w.end()); };
+    const auto one = [](size_t x) { return static_cast<int>(x); };
+    const std::pair<const char*, const V*> direct[] = {
+        {"plan.col0", &P.col0}, {"plan.rowptr", &P.rowptr}, {"plan.parent", &P.parent}, {"plan.level", &P.level},
+        {"plan.level_ptr", &P.level_ptr}, {"plan.level_sups", &P.level_sups}, {"plan.sup_of", &P.sup_of},
+        {"plan.yrow_ptr", &P.yrow_ptr}, {"plan.yrow_idx", &P.yrow_idx}, {"plan.unit_level_ptr", &P.unit_level_ptr},
+        {"plan.unit_sup", &P.unit_sup}, {"plan.kslot", &P.kslot}, {"plan.kslot_ptr", &P.kslot_ptr},
+        {"plan.tail_kslot_ptr", &P.tail_kslot_ptr},
+        {"panels.fu_sup", &S.panels.fu_sup}, {"panels.fu_j", &S.panels.fu_j}, {"panels.small_sups", &S.panels.small_sups},
+        {"panels.fu_ptr", &S.panels.fu_ptr}, {"panels.small_ptr", &S.panels.small_ptr},
+        {"panels.small1_cnt", &S.panels.small1_cnt},
+        {"chunks.chunk_sup", &S.chunks.chunk_sup}, {"chunks.chunk_r0", &S.chunks.chunk_r0},
+        {"chunks.sup_chunk0", &S.chunks.sup_chunk0}, {"chunks.chunk_ptr", &S.chunks.chunk_ptr},
+        {"order.sweep_sups", &S.order.sweep_sups}, {"order.leaf_cnt", &S.order.leaf_cnt},
+        {"order.leaf8_cnt", &S.order.leaf8_cnt},
+        {"sf.ybase", &S.sf.ybase}, {"sf.yrow_idx", &S.sf.yrow_idx}, {"sf.zbase", &S.sf.zbase}, {"sf.zpi", &S.sf.zpi},
+        {"sf.need", &S.sf.need}, {"sf.par", &S.sf.par}, {"sf.ylate_ptr", &S.sf.ylate_ptr},
+        {"sf.ylate_idx", &S.sf.ylate_idx}, {"sf.pre_col", &S.sf.pre_col}, {"sf.pre_ptr", &S.sf.pre_ptr},
+        {"sf.pre_idx", &S.sf.pre_idx},
+        {"visits.kslot", &S.visits.kslot}, {"visits.kptr", &S.visits.kptr}, {"visits.late_b", &S.visits.late_b},
+        {"gather.ck_u", &S.gather.ck_u}, {"gather.ck_b", &S.gather.ck_b}, {"gather.ck_e", &S.gather.ck_e},
+        {"gather.ck_part", &S.gather.ck_part}, {"gather.ck_q", &S.gather.ck_q}, {"gather.sp_u", &S.gather.sp_u},
+        {"gather.sp_p0", &S.gather.sp_p0}, {"gather.sp_n", &S.gather.sp_n}, {"gather.ck_ptr", &S.gather.ck_ptr},
+        {"gather.sp_ptr", &S.gather.sp_ptr}, {"gather.ck_kind", &S.gather.ck_kind},
+        {"tail.visit_ptr", &S.tail.visit_ptr}, {"tail.run_ptr", &S.tail.run_ptr},
+    };
+    for (const auto& d : direct)
+        if (name == d.first) return *d.second;
+    if (name == "plan.dims") return {P.T, P.nsup, P.nlevels, P.tail_c0, P.nt, P.ntb};
+    if (name == "plan.task_src") {     // per unit task: its source supernode
+        V v;
+        for (const ipo::TailTask& t : P.utasks) v.push_back(t.src);
+        return v;
+    }
+    if (name == "paths")
+        return {S.paths.visits, S.paths.chain_lead, S.paths.tail_run, S.paths.run_winpub, S.paths.small_leaves,
+                S.paths.sf_width};
+    if (name == "panels.split_level") return chars(S.panels.split_level);
+    if (name == "sf.items_f") return flat2(S.sf.items_f);
+    if (name == "sf.items_b") return flat2(S.sf.items_b);
+    if (name == "sf.dims") return {S.sf.sf_level, one(S.sf.ybuf_stride), one(S.sf.zpad_stride), S.sf.late_lists};
+    if (name == "visits.vis") {        // per visit: (group, unit, slot begin, slot end)
+        V v;
+        for (size_t g = 0; g < S.visits.vis.size(); g++)
+            for (const ipo::SchedInt3& e : S.visits.vis[g]) v.insert(v.end(), {one(g), e.x, e.y, e.z});
+        return v;
+    }
+    if (name == "gather.ck_wide") return chars(S.gather.ck_wide);
+    if (name == "gather.dims") return {one(S.gather.split_cnt), one(S.gather.partial_tiles)};
+    if (name == "chunks.dims") return {one(S.chunks.partial_stride)};
+    if (name == "work.launches") return {S.work.fwd_launches, S.work.bwd_launches};
+    if (name == "tail.visit_list") return V(S.tail.visit_list.begin(), S.tail.visit_list.end());
+    if (name == "tail.run_items") {
+        V v;
+        for (const ipo::SchedUint2& e : S.tail.run_items) { v.push_back(static_cast<int>(e.x)); v.push_back(static_cast<int>(e.y)); }
+        return v;
+    }
+    throw std::invalid_argument("kkt_schedule: unknown array '" + name + "'");
+}
+
 void synth_out(const ipo::SynthLP& o, int* kA, int* iA, double* A, double* b, double* c, double* xs, double* ys,
                double* ws, double* zs) {
     std::copy(o.kA.begin(), o.kA.end(), kA);
@@ -833,7 +900,7 @@ int ipo_hip_tail_run_schedule(int nt, int K, int L, int cap, unsigned* items, in
             throw std::invalid_argument("tail_schedule: nt gives " + std::to_string(ntb) + " block columns, the limit is " +
                                         std::to_string(ipo::kTailSchedMaxBlocks));
         std::vector<int> pv;
-        const std::vector<uint2> v = ipo::tail_run_schedule(ntb, nt, K, L, cap, pv);
+        const std::vector<ipo::SchedUint2> v = ipo::tail_run_schedule(ntb, nt, K, L, cap, pv);
         const int n = static_cast<int>(v.size());
         if (items)
             for (int i = 0; i < std::min(n, max_items); i++) {
@@ -842,6 +909,39 @@ int ipo_hip_tail_run_schedule(int nt, int K, int L, int cap, unsigned* items, in
             }
         if (ptr) std::copy(pv.begin(), pv.end(), ptr);
         return n;
+    } catch (const std::exception& e) {
+        set_err(e.what());
+        return -1;
+    }
+}
+
+long ipo_hip_kkt_schedule(int m, int n, const int* kA, const int* iA, int nforced, int cus, const char* name, int* out,
+                          long cap) {
+    try {
+        if (!name || cus <= 0) throw std::invalid_argument("kkt_schedule: bad arguments");
+        std::vector<int> kat, iat;
+        std::vector<double> at, a(kA[n], 1.0);
+        ipo::csc_transpose(m, n, kA, iA, a.data(), kat, iat, at);
+        const ipo::KktPlan P =
+            ipo::build_kkt_plan(m, n, kA, iA, kat.data(), iat.data(), nforced, ipo::device_tail_density());
+        const ipo::KktSchedule S = ipo::build_kkt_schedule(P, ipo::KktKnobs::from_env(), cus);
+        // one name: that array; several, comma-separated: each array's length, then its entries
+        // (a test reads a whole schedule from one build of the plan)
+        const std::string names(name);
+        std::vector<int> v;
+        if (names.find(',') == std::string::npos) {
+            v = schedule_array(P, S, names);
+        } else {
+            for (size_t b = 0; b <= names.size();) {
+                const size_t e = std::min(names.find(',', b), names.size());
+                const std::vector<int> w = schedule_array(P, S, names.substr(b, e - b));
+                v.push_back(static_cast<int>(w.size()));
+                v.insert(v.end(), w.begin(), w.end());
+                b = e + 1;
+            }
+        }
+        if (out) std::copy(v.begin(), v.begin() + std::min<long>(cap, static_cast<long>(v.size())), out);
+        return static_cast<long>(v.size());
     } catch (const std::exception& e) {
         set_err(e.what());
         return -1;

@@ -1536,21 +1536,10 @@ __device__ __forceinline__ void visit_tile512(const PlanView& p, const TailView&
 constexpr size_t kTailStepLds0 = sizeof(PanelLds) > sizeof(SyrkLds) ? sizeof(PanelLds) : sizeof(SyrkLds);
 constexpr size_t kTailStepLds = kTailStepLds0 > sizeof(PreLds) ? kTailStepLds0 : sizeof(PreLds);
 
-// Visits of launch t (tail_visit_cols): block column c receives the updates
-// of blocks 0 .. c - 2 in chunks of K = TailView::vk, the latest chunk in launch
-// c - 1, the one before in launch c - 2, ...: launch c - 1 - k applies blocks
-// [c - 1 - 4 (k + 1), c - 1 - 4 k) (clipped at 0) -- every block available
-// (b < t) and every column done before its panel, block c - 1 being the
-// panel's own pre-update.  Each entry still receives blocks 0, 1, ... in
-// order; the work is spread over the launches (late-as-possible, so the
-// early steps, once 3x the panel's time under the right-looking update, are
-// panel-bound) and a tile is read and written once per chunk, not per block.
-__host__ __device__ __forceinline__ int visit_hi(int t, int c, int K) { return c - 1 - K * (c - 1 - t); }
-
 // Step t of the look-ahead dense-tail factorisation, one launch:
 //   workgroups [0, gp):  panel of block column t (k_panel_w's body);
 //   the rest:            the visits of launch t, one tile each, columns
-//                        t + 1, t + 2, ... (visit_hi above).
+//                        t + 1, t + 2, ... (visit_hi, kkt_schedule.h).
 // Block column t holds every update from blocks <= t - 2 (earlier visits);
 // the panel workgroups apply block t - 1's to their own rows first
 // (panel_w_body's pre-update, k_tail_syrk's fragments and order).
@@ -1848,186 +1837,8 @@ k_panel_s1(PlanView p, const int* __restrict__ sups, int q0, int count, int dep)
 
 }  // namespace
 
-int tail_visit_tiles(int ntb, int t, int K) {
-    int n = 0;
-    for (int c = t + 1; c < ntb && visit_hi(t, c, K) > 0; c++) n += ntb - c;
-    return t > 0 ? n : 0;
-}
-
-// Launch t runs panel t on gp(t) workgroups beside its visits; with one
-// workgroup per CU (the kernel's LDS) a launch of more than `cap` workgroups
-// takes two rounds of visits: on dfl001 launches 21-37 under visit_hi's
-// chunks (up to 286 workgroups, 37-47 us against ~30).  Those launches carry
-// the first chunks of later columns' tiles (blocks 0 .. b1 - 1 with b1 <= 6),
-// which are ready from launch b1 on: moved, latest-first, into the latest
-// earlier launch with room.  Every tile keeps its chunks and their order (its
-// first chunk only comes earlier), so the factor is bitwise the same.
-std::vector<unsigned> tail_visit_schedule(int ntb, int nt, int K, int cap, bool xcd, std::vector<int>& ptr) {
-    struct V { int bi, c, b0, b1; };
-    std::vector<std::vector<V>> L(ntb);
-    std::vector<int> tot(ntb, 0);
-    for (int t = 0; t < ntb; t++) {
-        const int h = nt - t * PC;
-        tot[t] = std::max(1, (h + TR - 1) / TR - 1);          // launch_tail_step's panel workgroups
-        if (t == 0) continue;
-        for (int c = t + 1; c < ntb && visit_hi(t, c, K) > 0; c++) {
-            const int b1 = visit_hi(t, c, K), b0 = std::max(0, b1 - K);
-            for (int bi = c; bi < ntb; bi++) L[t].push_back({bi, c, b0, b1});
-        }
-        tot[t] += static_cast<int>(L[t].size());
-    }
-    for (int t = ntb - 1; t > 1; t--) {
-        while (tot[t] > cap) {
-            // a first chunk of this launch, the one ready earliest (then the
-            // farthest column: its tiles have the longest wait before their
-            // panel anyway)
-            int best = -1;
-            for (int q = 0; q < static_cast<int>(L[t].size()); q++) {
-                const V& v = L[t][q];
-                if (v.b0 != 0) continue;
-                if (best < 0 || v.b1 < L[t][best].b1 || (v.b1 == L[t][best].b1 && v.c > L[t][best].c)) best = q;
-            }
-            if (best < 0) break;
-            int dst = -1;
-            for (int u = t - 1; u >= std::max(1, L[t][best].b1); u--)
-                if (tot[u] < cap) { dst = u; break; }
-            if (dst < 0) break;
-            L[dst].push_back(L[t][best]);
-            tot[dst]++;
-            L[t].erase(L[t].begin() + best);
-            tot[t]--;
-        }
-    }
-    // XCD grouping (speed only, never correctness): workgroups b and b + 8
-    // share an XCD and its L2 (MI355X_MICROARCH.md, round-robin placement),
-    // and every visit of column c reads the same blocks L(c, b0 .. b1 - 1)
-    // (the B operand, W = L D): the visits of column c go to workgroup ids of
-    // one residue mod 8 where possible, so those blocks come from one L2
-    // (xcd; KktKnobs::visit_xcd)
-    std::vector<unsigned> out;
-    ptr.assign(ntb + 1, 0);
-    for (int t = 0; t < ntb; t++) {
-        ptr[t] = static_cast<int>(out.size());
-        std::vector<V> order;
-        if (xcd && !L[t].empty()) {
-            const int gp = tot[t] - static_cast<int>(L[t].size());
-            std::vector<std::vector<V>> q(8);
-            for (const V& v : L[t]) q[v.c % 8].push_back(v);
-            std::vector<size_t> head(8, 0);
-            for (size_t e = 0; e < L[t].size(); e++) {
-                int x = (gp + static_cast<int>(e)) % 8;
-                if (head[x] == q[x].size()) {           // this residue's columns are used up: the fullest other
-                    size_t best = 0;
-                    for (int y = 0; y < 8; y++)
-                        if (q[y].size() - head[y] > best) { best = q[y].size() - head[y]; x = y; }
-                }
-                order.push_back(q[x][head[x]++]);
-            }
-        } else {
-            order = L[t];
-        }
-        for (const V& v : order)
-            out.push_back(static_cast<unsigned>(v.bi) | static_cast<unsigned>(v.c) << 8 |
-                          static_cast<unsigned>(v.b0) << 16 | static_cast<unsigned>(v.b1) << 24);
-    }
-    ptr[ntb] = static_cast<int>(out.size());
-    return out;
-}
-
-// Chunks of column c of the persistent tail, latest first: blocks [0, c - 1)
-// (block c - 1 is its panel's pre-update), the latest L blocks one chunk (a
-// visit that must finish within one step: it needs block c - 2, final at the
-// end of step c - 2, before panel c), then K at a time downwards.
-static std::vector<std::pair<int, int>> run_chunks(int c, int K, int L) {
-    std::vector<std::pair<int, int>> v;
-    int b1 = c - 1;
-    for (int k = 0; b1 > 0; k++) {
-        const int b0 = std::max(0, b1 - (k == 0 ? L : K));
-        v.push_back({b0, b1});
-        b1 = b0;
-    }
-    return v;
-}
-
-std::vector<uint2> tail_run_schedule(int ntb, int nt, int K, int L, int cap, std::vector<int>& ptr) {
-    // the items hold bi, c, b0, b1, t and the chunk counts in 8 bits each:
-    // every caller keeps ntb <= kTailSchedMaxBlocks (the plan constructor,
-    // ipo_hip_tail_run_schedule), and a column has at most ntb chunks
-    static_assert(kTailSchedMaxBlocks <= 0xff, "tail_run_schedule packs block indices into 8 bits");
-    struct V { int bi, c, b0, b1, q; };
-    std::vector<std::vector<V>> Ls(ntb);
-    std::vector<int> tot(ntb, 0), nch(ntb, 0);
-    for (int c = 0; c < ntb; c++) {
-        const std::vector<std::pair<int, int>> ch = run_chunks(c, K, L);
-        nch[c] = static_cast<int>(ch.size());
-        // the k-th chunk from the top in launch c - 1 - k (its blocks < b1 <= c - 1 - k)
-        for (int k = 0; k < nch[c]; k++)
-            for (int bi = c; bi < ntb; bi++) Ls[c - 1 - k].push_back({bi, c, ch[k].first, ch[k].second, nch[c] - 1 - k});
-    }
-    for (int t = 0; t < ntb; t++) tot[t] = tail_gp(nt, t) + static_cast<int>(Ls[t].size());
-    // launches over `cap` items: first chunks (q = 0) into the latest earlier
-    // launch with room where they are ready (launch >= b1), as tail_visit_schedule
-    for (int t = ntb - 1; t > 1; t--) {
-        while (tot[t] > cap) {
-            int best = -1;
-            for (int i = 0; i < static_cast<int>(Ls[t].size()); i++) {
-                const V& v = Ls[t][i];
-                if (v.q != 0) continue;
-                if (best < 0 || v.b1 < Ls[t][best].b1 || (v.b1 == Ls[t][best].b1 && v.c > Ls[t][best].c)) best = i;
-            }
-            if (best < 0) break;
-            int dst = -1;
-            for (int u = t - 1; u >= std::max(1, Ls[t][best].b1); u--)
-                if (tot[u] < cap) { dst = u; break; }
-            if (dst < 0) break;
-            Ls[dst].push_back(Ls[t][best]);
-            tot[dst]++;
-            Ls[t].erase(Ls[t].begin() + best);
-            tot[t]--;
-        }
-    }
-    std::vector<uint2> out;
-    ptr.assign(ntb + 1, 0);
-    for (int t = 0; t < ntb; t++) {
-        ptr[t] = static_cast<int>(out.size());
-        for (int j = 0; j < tail_gp(nt, t); j++)
-            out.push_back(make_uint2(static_cast<unsigned>(j), static_cast<unsigned>(t) |
-                                                                  static_cast<unsigned>(nch[t]) << 8 | 1u << 31));
-        // column t + 1's visits first (its panel waits for them), then by column
-        std::vector<V>& vv = Ls[t];
-        std::stable_sort(vv.begin(), vv.end(), [t](const V& a, const V& b) {
-            const bool ua = a.c == t + 1, ub = b.c == t + 1;
-            if (ua != ub) return ua;
-            return a.c != b.c ? a.c < b.c : a.bi < b.bi;
-        });
-        for (const V& v : vv)
-            out.push_back(make_uint2(static_cast<unsigned>(v.bi) | static_cast<unsigned>(v.c) << 8 |
-                                         static_cast<unsigned>(v.b0) << 16 | static_cast<unsigned>(v.b1) << 24,
-                                     static_cast<unsigned>(t) | static_cast<unsigned>(v.q) << 8));
-    }
-    ptr[ntb] = static_cast<int>(out.size());
-    return out;
-}
-
 void launch_tail_run(const PlanView& pv, const TailView& tv, const TailRun& rc, hipStream_t s) {
     if (rc.n > 0) hipLaunchKernelGGL(k_tail_run, dim3(rc.n), dim3(PNT), 0, s, pv, tv, rc);
-}
-
-void tail_visit_work(int ntb, int nt, int K, double& flops, double& bytes) {
-    flops = bytes = 0.0;
-    for (int t = 1; t < ntb; t++)
-        for (int c = t + 1; c < ntb && visit_hi(t, c, K) > 0; c++) {
-            const int b1 = visit_hi(t, c, K), b0 = std::max(0, b1 - K);
-            for (int bi = c; bi < ntb; bi++) {
-                const double rows = std::min(TR, nt - bi * TR), cols = std::min(TR, nt - c * TR);
-                for (int b = b0; b < b1; b++) {
-                    const double k = std::min(PC, nt - b * PC);
-                    flops += 2.0 * rows * cols * k;
-                    bytes += 8.0 * k * (rows + cols);          // L rows of bi and of c (W = L D formed on load)
-                }
-                bytes += 16.0 * rows * cols;                   // one read-modify-write of the tile
-            }
-        }
 }
 
 void launch_tail_step(const PlanView& pv, const TailView& tv, int t, hipStream_t s) {

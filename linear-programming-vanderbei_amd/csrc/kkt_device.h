@@ -18,15 +18,12 @@
 #include "exchange.h"
 #include "kkt_knobs.h"
 #include "kkt_plan.h"
+#include "kkt_schedule.h"
 
 namespace ipo {
 
 // Device view of the dense tail (see kkt_plan.h): S = nt x nt column-major.
-// (kTailVisitBlocks, kTailVisitLatest: kkt_knobs.h)
-// most block columns of a scheduled tail: the schedules pack block indices
-// and chunk counts into 8 bits each (tail_visit_schedule, tail_run_schedule);
-// a larger tail takes the per-step launches with the visit_hi formula
-constexpr int kTailSchedMaxBlocks = 255;
+// (kTailVisitBlocks, kTailVisitLatest: kkt_knobs.h; kTailSchedMaxBlocks: kkt_schedule.h)
 struct TailView {
     double* S;
     int nt, ntb, tc;
@@ -70,11 +67,7 @@ struct TailRun {
 // one published tile window: 16 columns of 64 rows of L, then the 16 pivots d
 constexpr int kTailPubWin = 16 * 64 + 16;
 
-// Device-time phases of the KKT core (timing mode), with the algorithmic
-// work of one occurrence (one factorisation / one substitution sweep).
-// kPhTail: the look-ahead dense-tail factor (k_tail_pr and its repair launches).
-enum KktPhase { kPhGather = 0, kPhDiag, kPhTrsm, kPhSyrk, kPhForward, kPhBackward, kPhTail, kNumPhases };
-
+// (KktPhase, the device-time phases of the KKT core: kkt_schedule.h)
 struct KktTimers {
     double phase_ms[kNumPhases] = {};       // accumulated device time per phase
     long phase_launches[kNumPhases] = {};   // kernel launches per phase
@@ -98,6 +91,8 @@ struct QBlock {
     const double* Q = nullptr;
     int qmax = 1;
 };
+
+struct PlanView;   // kkt_kernels.h
 
 class KktDevice {
   public:
@@ -181,23 +176,22 @@ class KktDevice {
 
   private:
     const KktKnobs knobs_ = KktKnobs::from_env();   // every runtime knob, read once (kkt_knobs.h)
-    // the constructor's steps, in order (each returns / takes what crosses steps)
+    // the constructor's steps, in order: each calls its pure function of
+    // kkt_schedule.h, uploads the arrays and keeps the host part in h_
+    // (what crosses steps is passed; the parts are locals of their step)
     void upload_plan(const int* kA, const int* iA, const double* A, const std::vector<int>& kat,
                      const std::vector<int>& iat, const std::vector<double>& at, const QBlock* qb);
     void build_panel_units();
-    void build_solve_chunks();
-    void build_sweep_order();
-    // deep trees: the sparse units' k-slots in visit order (build_visit_slots; empty without visits)
-    struct VisitSlots {
-        std::vector<int> kslot, kptr, late_b;     // the slots; per unit: its range's end, its first late slot
-        std::vector<std::vector<int3>> vis;       // per gather group: (unit, slot begin, slot end)
-    };
-    VisitSlots build_visit_slots() const;
+    SolveChunks build_solve_chunks();
+    void build_sweep_order(const SolveChunks& ch);
+    void build_sync_free_plan(const SolveChunks& ch, int cus);
     void build_gather_chunks(const VisitSlots& vs);
     void count_work();
     void build_slot_records(const std::vector<int>& kslot_v);
     void setup_tail(int cus);
     void alloc_numeric();
+    KktLaunch h_;                  // what the launch code reads of the schedule on the host
+    PlanView plan_view() const;
     // the host repair backs the look-ahead panel's dependent pivots (TailView::dep):
     // not without the fused kernels, not in a sharded solve
     bool tail_repair() const { return use_panel_ && !xch_ && knobs_.tail_repair; }
@@ -210,10 +204,8 @@ class KktDevice {
     void sweep_blocked(double* dz, const double* epsp);
     void tail_rhs_begin(double* dz, int R);
     void tail_rhs_end(double* dz, int R);
-    size_t ybuf_stride_ = 1, partial_stride_ = 1;
     DevBuf<int> dIncons_;          // per right-hand side: inconsistent-system flag
     int launch_gather(const struct PlanView& pv, const TailView& tv, int tail, int group, hipStream_t s);
-    int fwd_launches_ = 0, bwd_launches_ = 0;   // kernel launches per substitution sweep
     void launch_reduce_maxabs2(const double* a, int na, const double* b, int nb, double* dst);
 
     int m_, n_, T_;
@@ -270,48 +262,34 @@ class KktDevice {
     DevBuf<int> dyrow_ptr_, dyrow_idx_;
     // deep trees: the narrow range's update lists without the values from
     // below the range, and those values' lists for the pre-pass (k_fwd_pre)
-    int pre_cols_ = 0;
     DevBuf<int> dylate_ptr_, dylate_idx_, dpre_col_, dpre_ptr_, dpre_idx_;
     DevBuf<double> dYbuf_;
     // sync-free top levels of the sweeps (k_fwd_sf / k_bwd_sf)
-    void build_sync_free_plan(int cus);
-    int sf_level_ = 0;                    // first level of the range (nlevels: none)
-    int nsf_f_ = 0, nsf_b_ = 0, sf_grid_ = 1;
+    int sf_grid_ = 1;
     int sf_fwd_epoch_ = 0, sf_bwd_epoch_ = 0;
     long long sf_ticket_next_[2] = {0, 0};   // work-item ticket counters (forward, backward): next launch's base
-    std::vector<int2> h_sf_items_f_;         // forward sync-free items (host copy, developer stamps)
+#ifdef IPO_SF_STAMPS
+    std::vector<SchedInt2> h_sf_items_f_;    // forward sync-free items (host copy, developer stamps)
+#endif
     int sf_tbase(int d, int nitems);
-    size_t zpad_stride_ = 1;
-    std::vector<int> h_chunk0_;           // per supernode: first solve chunk (-1: not chunked)
     DevBuf<int2> dsf_items_f_, dsf_items_b_;
     DevBuf<int> dsf_need_, dsf_par_, dsf_zbase_, dsf_zpi_, dsf_fcnt_, dsf_fflag_, dsf_bcnt_, dsf_bflag_, dsf_ticket_;
     DevBuf<int> dybase_;                  // per supernode: first ybuf slot of its update values
     DevBuf<double> dZpad_;                // padded z slices of the range, 2 right-hand sides
-    std::vector<int> fu_ptr_;             // per level: fused panel units [fu_ptr_[l], fu_ptr_[l+1])
-    DevBuf<int> dfu_sup_, dfu_j_;         // fused panel unit -> supernode, tile pair index
-    std::vector<int> small_ptr_;          // per level: small panels [small_ptr_[l], small_ptr_[l+1]) (k_panel_s)
-    std::vector<char> split_level_;       // per level: k_diag + k_trsm instead of the fused panels (wide levels)
-    std::vector<int> small1_cnt_;         // per level: leading single-column small panels of <= 8 rows (k_panel_s1)
-    DevBuf<int> dsmall_sups_;
+    DevBuf<int> dfu_sup_, dfu_j_;         // fused panel unit -> supernode, tile pair index (per level: h_.fu_ptr)
+    DevBuf<int> dsmall_sups_;             // small panels (per level: h_.small_ptr)
     const bool use_panel_ = knobs_.panel; // fused diagonal-block + panel kernels
     bool factor_pass(const double* dE, const double* dD, bool fused, bool tail_fused);
     void enqueue_levels(const PlanView& pv, const TailView& tv, bool fused, hipStream_t s);
     bool finish_pass(bool fused);
     void repair_tail();
-    std::vector<int> chunk_ptr_;          // per level: solve chunks [chunk_ptr_[l], chunk_ptr_[l+1])
-    std::vector<int> leaf_cnt_;           // per level: leading single-column supernodes of dsweep_sups_
-    std::vector<int> leaf8_cnt_;          // per level: the first of them, small leaves (k_fwd_leaf8 / k_bwd_leaf8)
-    int small_leaves() const;             // knobs_.small_leaves, unset: kSmallLeafMinCount
     DevBuf<int> dsweep_sups_;             // level_sups in sweep order (leaves first on unchunked levels)
     DevBuf<int> dchunk_sup_, dchunk_r0_, dsup_chunk0_;
     DevBuf<double> dPartial_;    // backward partial sums, one 64-vector per chunk
     // split-K gather chunks per group (sparse level l, group nlevels = tail)
-    bool visits_ = false;
     int gst_group_ = knobs_.gather_stamps, gst_n_ = 0;   // developer gather stamps: one launch, then -1
-    DevBuf<long long> dGStamp_;        // deep trees: early gather slots as visits in lower levels' launches
-    std::vector<int> ck_kind_;   // per gather group: 0 k_update, 1 k_update_flat, 2 k_update_quad
-    std::vector<bool> ck_wide_;   // ck_flat_: k_update_flat (latency-bound launches of deep trees)      // per gather group: k_update<4> (few chunks, units split >= 4 ways)
-    std::vector<int> ck_ptr_, sp_ptr_;
+    DevBuf<long long> dGStamp_;
+    // (per group: h_.ck_ptr; h_.ck_kind 0 k_update, 1 k_update_flat, 2 k_update_quad; h_.ck_wide k_update<4>)
     DevBuf<int> dck_u_, dck_b_, dck_e_, dck_part_, dsp_u_, dsp_p0_, dsp_n_;
     DevBuf<int> dck_q_;          // split-unit index of each chunk (-1: unsplit)
     DevBuf<int> dSplitCnt_;      // arrival counters of the split units (fused split-K), zero between launches
@@ -321,19 +299,14 @@ class KktDevice {
     DevBuf<SlotRec> dslot_rec_, dtail_slot_rec_;   // per gather k-slot record (sparse units, dense tail)
     DevBuf<unsigned long long> dChainGran_;   // dense-tail sweep chains: z of every block as epoch-tagged granules
     int chain_epoch_ = 0;      // the chains' launch epoch (one per launch, never reused)
-    bool chain_lead_ = false;  // forward dense-tail sweep by one lead workgroup + helpers (k_tail_fwd_lead)
     DevBuf<int> dtail_task_ptr_, dtail_kslot_, dtail_kslot_ptr_;
     DevBuf<int> dlead_ticket_;         // k_tail_fwd_lead's role tickets (never reset within a run)
     long long lead_ticket_next_ = 0;
     DevBuf<unsigned> dvisit_list_;     // TailView::vlist (tail_visit_schedule; knobs_.visit_sched off: none)
-    std::vector<int> visit_ptr_;       // TailView::vptr
     // the dense tail as one persistent launch (k_tail_run; knobs_.tail_run off: one launch per step)
-    bool tail_run_ = false;
-    DevBuf<uint2> drun_items_;         // tail_run_schedule
-    std::vector<int> run_ptr_;         // first item of each launch
+    DevBuf<uint2> drun_items_;         // tail_run_schedule (first item of each launch: h_.run_ptr)
     DevBuf<int> drun_cnt_;             // ticket, pdone[ntb], vseq[ntb * ntb], pread[ntb]
     // the run's window hand-off (TailRun::pub; knobs_.tail_winpub)
-    bool run_winpub_ = false;
     DevBuf<double> drun_pub_;          // [2 * ntb * 4 * kTailPubWin]
     DevBuf<int> drun_wflag_;           // [ntb * ntb * 4], zeroed once
     int run_epoch_ = 0;

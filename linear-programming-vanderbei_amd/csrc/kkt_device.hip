@@ -1254,8 +1254,6 @@ k_bwd_leaf(PlanView p, const int* __restrict__ sups, int q0, int cnt, SweepVecs 
 // (one `+ 0.0`: further ones change nothing); k_bwd_leaf's wave_sum reaches
 // lane 0 through lanes 0-7 the same way (three adds of +0.0, then the
 // row-down steps 4, 2, 1).  Bitwise the one-wave kernels.
-constexpr int kSmallLeaf = 8;
-constexpr int kSmallLeafMinCount = 32768;     // per level, else one wave per leaf
 
 template <int R>
 __global__ void __launch_bounds__(NT)
@@ -1689,7 +1687,6 @@ k_tail_bwd(PlanView p, TailView tv, int kb, double* __restrict__ z, const double
 // per CU is enforced with dynamic LDS.  Every workgroup only waits on blocks
 // of lower rank in its own launch order, so the grid drains as long as it
 // is resident (ntb <= kChainMaxBlocks).
-constexpr int kChainMaxBlocks = 200;
 constexpr size_t kChainLds = 96 * 1024;
 static_assert(2 * PC * (PC + 1) * sizeof(double) <= kChainLds, "k_tail_bwd_chain scratch");
 
@@ -2463,7 +2460,7 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
 }
 
 // ------------------------------------------- sync-free sweeps, top levels
-// The narrow top of the elimination tree (levels >= sf_level_, a few
+// The narrow top of the elimination tree (levels >= h_.sf_level, a few
 // supernodes each) in one persistent launch per direction instead of one or
 // two launches per level.  One workgroup per CU (dynamic LDS).  Workgroups
 // draw the work items in list order from a global ticket counter (one
@@ -2474,9 +2471,14 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
 // whatever share of the CUs the launch gets (co-tenant kernels, several
 // shards on one device).  The counter is never reset within a run: each
 // launch draws exactly nitems + gridDim.x tickets (every workgroup stops at
-// its first ticket past the list), so the host passes the launch's base.  Items: (s, -1) a whole supernode, (s, -2) the
-// diagonal part (forward) / the finish (backward) of a chunked supernode,
-// (s, c >= 0) its 64-row chunk c.  Hand-offs follow MI355X_MICROARCH.md
+// its first ticket past the list), so the host passes the launch's base.
+// Items (build_sync_free_plan, kkt_schedule.cpp): (s, -1) a whole supernode,
+// (s, c >= 0) solve chunk c (64 rows) of a supernode on a chunked level.
+// Forward, every chunk item solves the diagonal part itself; backward, the
+// chunk whose arrival comes last finishes the supernode.  The lists hold no
+// other code: k_fwd_sf takes any code but -1 as a chunk index, and the
+// (s, -2) finish item k_bwd_sf still has a branch for is never built.
+// Hand-offs follow MI355X_MICROARCH.md
 // (inter-workgroup visibility, table row 1): the producer writes the values
 // with sc1 stores, waits vmcnt(0), joins a barrier, and one lane adds to
 // the consumer's counter or stores a flag (agent scope); the consumer polls
@@ -3105,11 +3107,7 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
     mark("transpose");
     plan_ = build_kkt_plan(m, n, kA, iA, kat.data(), iat.data(), nforced, tail_density, qb ? &qpat : nullptr);
     mark("ordering + symbolic plan");
-    // the paths that the knobs and the plan select together
-    visits_ = knobs_.deep_tree(plan_.nlevels);
-    chain_lead_ = knobs_.chain_lead && plan_.nt > 0 && plan_.ntb <= kChainMaxBlocks;
-    tail_run_ = knobs_.tail_run && plan_.nt > 0 && plan_.ntb <= kTailSchedMaxBlocks;
-    run_winpub_ = knobs_.tail_winpub && tail_run_;
+    h_.paths = kkt_paths(plan_, knobs_);
     int dev = 0, cus = 0;
     IPO_HIP_CHECK(hipGetDevice(&dev));
     IPO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -3117,13 +3115,15 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
     mark("upload_plan");
     build_panel_units();
     mark("build_panel_units");
-    build_solve_chunks();
-    mark("build_solve_chunks");
-    build_sweep_order();
-    mark("build_sweep_order");
-    build_sync_free_plan(cus);
-    mark("build_sync_free_plan");
-    const VisitSlots vs = build_visit_slots();
+    {
+        const SolveChunks ch = build_solve_chunks();     // its per-supernode part, for the next two steps
+        mark("build_solve_chunks");
+        build_sweep_order(ch);
+        mark("build_sweep_order");
+        build_sync_free_plan(ch, cus);
+        mark("build_sync_free_plan");
+    }
+    const VisitSlots vs = build_visit_slots(plan_, knobs_, h_.paths);
     mark("build_visit_slots");
     build_gather_chunks(vs);
     mark("build_gather_chunks");
@@ -3189,423 +3189,94 @@ void KktDevice::upload_plan(const int* kA, const int* iA, const double* A, const
     dlevel_sups_.upload(plan_.level_sups, s);
 }
 
-int KktDevice::small_leaves() const { return knobs_.small_leaves < 0 ? kSmallLeafMinCount : knobs_.small_leaves; }
-
-// Fused panel units (k_panel_w): per supernode max(1, tiles - 1) workgroups,
-// workgroup j holding the diagonal block and 64-row tile j + 1
-// (supernodes of at most 16 columns and 64 rows go to the one-wave
-// small-panel kernel instead: list small_sups_, per level small_ptr_)
+// Fused panel units and small panels per level (kkt_schedule.h)
 void KktDevice::build_panel_units() {
     hipStream_t s = stream_;
-    std::vector<int> fs, fj, ss;
-    fu_ptr_.assign(plan_.nlevels + 1, 0);
-    small_ptr_.assign(plan_.nlevels + 1, 0);
-    for (int l = 0; l < plan_.nlevels; l++) {
-        for (int q = plan_.level_ptr[l]; q < plan_.level_ptr[l + 1]; q++) {
-            const int sp = plan_.level_sups[q];
-            const int nc = plan_.col0[sp + 1] - plan_.col0[sp];
-            const int h = nc + plan_.rowptr[sp + 1] - plan_.rowptr[sp];
-            if (nc <= 16 && h <= kTileRows) { ss.push_back(sp); continue; }
-            const int nw = std::max(1, ceil_div(h, kTileRows) - 1);
-            for (int j = 0; j < nw; j++) { fs.push_back(sp); fj.push_back(j); }
-        }
-        fu_ptr_[l + 1] = static_cast<int>(fs.size());
-        small_ptr_[l + 1] = static_cast<int>(ss.size());
-    }
-    // Levels whose fused units outnumber their supernodes many times
-    // over and fill the device several times (the separator levels of
-    // nested dissection: 1,000-3,500 units, 7-14 per supernode) run the
-    // per-phase kernels instead: the fused units each refactor their
-    // supernode's diagonal block, k_diag factors it once and k_trsm's
-    // tiles only read it.  The same operations on every entry in the
-    // same order (the IPO_HIP_PANEL=0 path), so bitwise the fused one.
-    // IPO_HIP_PANEL_SPLIT: the unit count from which a level splits (0: never)
-    const int split_min = knobs_.panel_split;
-    split_level_.assign(plan_.nlevels, 0);
-    for (int l = 0; l < plan_.nlevels && split_min > 0; l++) {
-        const int nfu = fu_ptr_[l + 1] - fu_ptr_[l];
-        int nsup = 0;
-        for (int q = fu_ptr_[l]; q < fu_ptr_[l + 1]; q++) nsup += fj[q] == 0;
-        split_level_[l] = nfu >= split_min && nfu >= 4 * nsup;
-    }
-    // single-column small panels of <= 8 rows first in each level's list,
-    // eight to a wave (k_panel_s1) on levels of many of them (the leaf
-    // sweeps' threshold, IPO_HIP_SMALL_LEAVES)
-    small1_cnt_.assign(plan_.nlevels, 0);
-    const int thr = small_leaves();
-    for (int l = 0; l < plan_.nlevels && thr > 0; l++) {
-        const auto b = ss.begin() + small_ptr_[l], e = ss.begin() + small_ptr_[l + 1];
-        const auto mid = std::stable_partition(b, e, [&](int sp) {
-            return plan_.col0[sp + 1] - plan_.col0[sp] == 1 && 1 + plan_.rowptr[sp + 1] - plan_.rowptr[sp] <= 8;
-        });
-        if (mid - b >= thr) small1_cnt_[l] = static_cast<int>(mid - b);
-    }
-    dfu_sup_.upload(fs, s);
-    dfu_j_.upload(fj, s);
-    dsmall_sups_.upload(ss, s);
+    PanelUnits pu = ipo::build_panel_units(plan_, knobs_, h_.paths);
+    dfu_sup_.upload(pu.fu_sup, s);
+    dfu_j_.upload(pu.fu_j, s);
+    dsmall_sups_.upload(pu.small_sups, s);
     IPO_HIP_CHECK(hipStreamSynchronize(s));
+    h_.fu_ptr = std::move(pu.fu_ptr);
+    h_.small_ptr = std::move(pu.small_ptr);
+    h_.split_level = std::move(pu.split_level);
+    h_.small1_cnt = std::move(pu.small1_cnt);
 }
 
-// Solve chunks: levels holding a panel with more than kChunkRows rows below
-// its diagonal block are solved in 64-row chunks (two launches each way)
-void KktDevice::build_solve_chunks() {
+// Solve chunks of the chunked levels; returns what the sweep order and the
+// sync-free plan read of them (the chunk lists themselves are dropped)
+SolveChunks KktDevice::build_solve_chunks() {
     hipStream_t s = stream_;
-    constexpr int kChunkRows = 128;
-    std::vector<int> csup, cr0, chunk0(plan_.nsup, -1);
-    chunk_ptr_.assign(plan_.nlevels + 1, 0);
-    for (int l = 0; l < plan_.nlevels; l++) {
-        bool big = false;
-        for (int q = plan_.level_ptr[l]; q < plan_.level_ptr[l + 1]; q++) {
-            const int sp = plan_.level_sups[q];
-            big |= plan_.rowptr[sp + 1] - plan_.rowptr[sp] > kChunkRows;
-        }
-        if (big)
-            for (int q = plan_.level_ptr[l]; q < plan_.level_ptr[l + 1]; q++) {
-                const int sp = plan_.level_sups[q], hb = plan_.rowptr[sp + 1] - plan_.rowptr[sp];
-                chunk0[sp] = static_cast<int>(csup.size());
-                for (int r0 = 0; r0 < hb; r0 += 64) { csup.push_back(sp); cr0.push_back(r0); }
-            }
-        chunk_ptr_[l + 1] = static_cast<int>(csup.size());
-    }
-    dchunk_sup_.upload(csup, s);
-    dchunk_r0_.upload(cr0, s);
-    dsup_chunk0_.upload(chunk0, s);
-    partial_stride_ = csup.empty() ? 1 : csup.size() * kPanelCols;
-    dPartial_.alloc(2 * partial_stride_);
-    IPO_HIP_CHECK(hipStreamSynchronize(s));   // csup / cr0 / chunk0 are stack vectors
-    h_chunk0_ = chunk0;
-}
-
-// Sweep order of each level: on levels without solve chunks the
-// single-column supernodes with <= 64 rows below come first (one wave
-// each, k_fwd_leaf / k_bwd_leaf), the rest after them
-void KktDevice::build_sweep_order() {
-    hipStream_t s = stream_;
-    std::vector<int> ss(plan_.level_sups);
-    leaf_cnt_.assign(plan_.nlevels, 0);
-    leaf8_cnt_.assign(plan_.nlevels, 0);
-    const int min8 = small_leaves();
-    for (int l = 0; l < plan_.nlevels; l++) {
-        if (chunk_ptr_[l + 1] > chunk_ptr_[l]) continue;
-        const auto b = ss.begin() + plan_.level_ptr[l], e = ss.begin() + plan_.level_ptr[l + 1];
-        const auto mid = std::stable_partition(b, e, [&](int sp) {
-            return plan_.col0[sp + 1] - plan_.col0[sp] == 1 && plan_.rowptr[sp + 1] - plan_.rowptr[sp] <= 64;
-        });
-        leaf_cnt_[l] = static_cast<int>(mid - b);
-        if (min8 > 0) {   // the small ones first (k_fwd_leaf8 / k_bwd_leaf8)
-            const auto mid8 = std::stable_partition(b, mid, [&](int sp) {
-                const int c = plan_.col0[sp];
-                return plan_.rowptr[sp + 1] - plan_.rowptr[sp] <= kSmallLeaf &&
-                       plan_.yrow_ptr[c + 1] - plan_.yrow_ptr[c] <= kSmallLeaf;
-            });
-            leaf8_cnt_[l] = static_cast<int>(mid8 - b);
-            // a wave of eight leaves touches eight times the cache lines
-            // per load: slower on latency-bound levels (dfl001's sweeps
-            // 4 ms slower per solve), faster from tens of thousands of
-            // leaves on (configs[3]: 10^6)
-            if (leaf8_cnt_[l] < min8) leaf8_cnt_[l] = 0;
-        }
-    }
-    dsweep_sups_.upload(ss, s);
+    SolveChunks ch = ipo::build_solve_chunks(plan_);
+    dchunk_sup_.upload(ch.chunk_sup, s);
+    dchunk_r0_.upload(ch.chunk_r0, s);
+    dsup_chunk0_.upload(ch.sup_chunk0, s);
+    h_.partial_stride = ch.partial_stride;
+    dPartial_.alloc(2 * h_.partial_stride);
     IPO_HIP_CHECK(hipStreamSynchronize(s));
+    h_.chunk_ptr = ch.chunk_ptr;
+    ch.chunk_sup = {};
+    ch.chunk_r0 = {};
+    return ch;
 }
 
-// Deep elimination trees (at least kVisitLevels levels, e.g. the banded
-// BASELINE configs[3]: 2,785 levels, most of them one or two 64-column
-// supernodes): a level's gather would wait on every descendant's update,
-// although 93 % of its k-slots come from supernodes finished several
-// levels earlier.  There each unit's slots are ordered by the level of
-// their source (stable), and only the slabs that hold a source of the
-// level just below ("late") stay in the unit's own level's gather; the
-// earlier slabs become visits of at most kVisitSlots slots, scheduled as
-// late as their sources allow into the gather launches of the levels
-// below (one visit per unit per launch, each a read-modify-write of the
-// unit's tile in slot order).  The level chain then waits per level on
-// one small gather and the panel, the visits ride in the same launches
-// beside them.  IPO_HIP_VISITS=1/0 forces the schedule on / off
-// (KktKnobs::deep_tree); without it the result is empty.
-KktDevice::VisitSlots KktDevice::build_visit_slots() const {
-    VisitSlots v;
-    v.vis.resize(plan_.nlevels + 1);
-    if (!visits_) return v;
-    const int nu = static_cast<int>(plan_.unit_sup.size());
-    const int visit_slabs = knobs_.visit_slabs;
-    v.kptr.assign(nu + 1, 0);
-    v.late_b.assign(nu, 0);
-    std::vector<std::pair<int, int>> sl;   // (source level, slot)
-    std::vector<int> rl;
-    for (int l = 1; l < plan_.nlevels; l++)
-        for (int u = plan_.unit_level_ptr[l]; u < plan_.unit_level_ptr[l + 1]; u++) {
-            sl.clear();
-            for (int i = plan_.kslot_ptr[u]; i < plan_.kslot_ptr[u + 1]; i++) {
-                const int k = plan_.kslot[i];
-                if (k >= 0) sl.push_back({plan_.level[plan_.utasks[k >> 6].src], k});
-            }
-            std::stable_sort(sl.begin(), sl.end(),
-                             [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
-            const int kb = static_cast<int>(v.kslot.size());
-            rl.clear();
-            for (size_t i = 0; i < sl.size(); i++) {
-                v.kslot.push_back(sl[i].second);
-                if (i % kSlab == 0) rl.push_back(sl[i].first);
-                else rl.back() = std::max(rl.back(), sl[i].first);
-            }
-            while (v.kslot.size() % kSlab) v.kslot.push_back(-1);
-            v.kptr[u + 1] = static_cast<int>(v.kslot.size());
-            const int nsl = static_cast<int>(rl.size());
-            int j = nsl;
-            while (j > 0 && rl[j - 1] >= l - 1) j--;
-            v.late_b[u] = kb + kSlab * j;
-            // early slabs [0, j), backwards, as late as their sources allow
-            int t = l - 1, end = j, cur = j;
-            while (cur > 0) {
-                if (end - cur >= visit_slabs && rl[cur - 1] <= t - 2) {
-                    v.vis[t].push_back(make_int3(u, kb + kSlab * cur, kb + kSlab * end));
-                    t--;
-                    end = cur;
-                }
-                cur--;
-            }
-            if (end > 0) v.vis[t].push_back(make_int3(u, kb, kb + kSlab * end));
-        }
-    // groups visit their units in unit order
-    for (auto& g : v.vis)
-        std::sort(g.begin(), g.end(), [](const int3& a, const int3& b) { return a.x < b.x; });
-    return v;
+void KktDevice::build_sweep_order(const SolveChunks& ch) {
+    hipStream_t s = stream_;
+    SweepOrder so = ipo::build_sweep_order(plan_, h_.paths, ch);
+    dsweep_sups_.upload(so.sweep_sups, s);
+    IPO_HIP_CHECK(hipStreamSynchronize(s));
+    h_.leaf_cnt = std::move(so.leaf_cnt);
+    h_.leaf8_cnt = std::move(so.leaf8_cnt);
 }
 
 // Gather chunks (split K): groups = sparse levels (with their visits, vs),
 // then the dense tail
 void KktDevice::build_gather_chunks(const VisitSlots& vs) {
     hipStream_t s = stream_;
-    // flat gathers (k_update_flat) for the latency-bound launches of
-    // deep trees: IPO_HIP_GATHER_FLAT=0 never, 1 (default) deep trees,
-    // 2 every launch of at most kFlatMaxChunks chunks
-    const int flat_mode = knobs_.gather_flat;
-    // quadrant gathers (k_update_quad) on the narrow levels of deep trees
-    // (IPO_HIP_GATHER_QUAD=0: off)
-    const bool quad_mode = knobs_.gather_quad;
-    std::vector<int> cu, cb, ce, cp, cq, su, sp0, sn;
-    ck_ptr_.assign(plan_.nlevels + 2, 0);
-    sp_ptr_.assign(plan_.nlevels + 2, 0);
-    size_t max_part = 0;
-    const int wg_target = 512;
-    const int min_chunk = knobs_.min_chunk;
-    // units [u0, u1), slots [kbeg(u), kend(u)) each, then the group's visits
-    // a sparse unit's 32 x 32 quadrants that hold lower-triangle entries (k_update_quad)
-    auto quadrants = [&](int u, int kb, int ke) {
-        const int sp = plan_.unit_sup[u], t = plan_.unit_tile[u];
-        const int nc = plan_.col0[sp + 1] - plan_.col0[sp], h = nc + plan_.rowptr[sp + 1] - plan_.rowptr[sp];
-        const int nrow = std::min(kTileRows, h - t * kTileRows);
-        for (int q = 0; q < 4; q++) {
-            const int qr = q & 1, qc = q >> 1;
-            if (32 * qr >= nrow || 32 * qc >= nc || (t == 0 && qc > qr)) continue;
-            cu.push_back(u); cb.push_back(kb); ce.push_back(ke); cp.push_back(-1 - q); cq.push_back(-1);
-        }
-    };
-    auto group = [&](int u0, int u1, auto kbeg, auto kend, const std::vector<int3>* visits) {
-        const long nck0 = static_cast<long>(cu.size());
-        long sumk = 0, nun = 0;
-        for (int u = u0; u < u1; u++) { sumk += kend(u) - kbeg(u); nun += kend(u) > kbeg(u); }
-        // deep trees' narrow levels: quadrant gathers, one chunk per unit
-        const bool quad = quad_mode && visits && nun + static_cast<long>(visits->size()) <= kQuadMaxUnits;
-        if (quad) {
-            for (int u = u0; u < u1; u++)
-                if (kend(u) > kbeg(u)) quadrants(u, kbeg(u), kend(u));
-            for (const int3& v : *visits) quadrants(v.x, v.y, v.z);
-            ck_wide_.push_back(false);
-            ck_kind_.push_back(2);
-            return;
-        }
-        // aim at >= wg_target workgroups per launch, chunks of min_chunk..512 slots
-        long kmax = (sumk / wg_target + kSlab - 1) / kSlab * kSlab;
-        kmax = std::max<long>(min_chunk, std::min<long>(kMaxChunkSlots, kmax));
-        int np = 0, mx = 0;
-        for (int u = u0; u < u1; u++) {
-            const int kb = kbeg(u), ke = kend(u);
-            if (ke == kb) continue;
-            const int nch = static_cast<int>((ke - kb + kmax - 1) / kmax);
-            mx = std::max(mx, nch);
-            if (nch > 1) { su.push_back(u); sp0.push_back(np); sn.push_back(nch); }
-            for (int j = 0; j < nch; j++) {
-                cu.push_back(u);
-                cb.push_back(kb + static_cast<int>(j * kmax));
-                ce.push_back(std::min<int>(ke, kb + static_cast<int>((j + 1) * kmax)));
-                cp.push_back(nch > 1 ? np++ : -1);
-                cq.push_back(nch > 1 ? static_cast<int>(su.size()) - 1 : -1);
-            }
-        }
-        if (visits)
-            for (const int3& v : *visits) {
-                cu.push_back(v.x); cb.push_back(v.y); ce.push_back(v.z); cp.push_back(-1); cq.push_back(-1);
-            }
-        max_part = std::max<size_t>(max_part, np);
-        // a group of few chunks (about one per CU: occupancy does not
-        // matter) whose units are split many ways waits on its partial
-        // sums: sum them several at a time
-        ck_wide_.push_back(mx >= 4 && static_cast<long>(cu.size()) - nck0 <= 512);
-        ck_kind_.push_back(quad ? 2 : (flat_mode == 2 || (flat_mode == 1 && visits_)) &&
-                                           static_cast<long>(cu.size()) - nck0 <= kFlatMaxChunks ? 1 : 0);
-    };
-    const std::vector<int>& kp = plan_.kslot_ptr;
-    ck_wide_.clear();
-    ck_kind_.clear();
-    for (int l = 0; l < plan_.nlevels; l++) {
-        if (l == 0) { ck_wide_.push_back(false); ck_kind_.push_back(0); }
-        else if (visits_)
-            group(plan_.unit_level_ptr[l], plan_.unit_level_ptr[l + 1], [&](int u) { return vs.late_b[u]; },
-                  [&](int u) { return vs.kptr[u + 1]; }, &vs.vis[l]);
-        else
-            group(plan_.unit_level_ptr[l], plan_.unit_level_ptr[l + 1], [&](int u) { return kp[u]; },
-                  [&](int u) { return kp[u + 1]; }, nullptr);
-        ck_ptr_[l + 1] = static_cast<int>(cu.size());
-        sp_ptr_[l + 1] = static_cast<int>(su.size());
-    }
-    const std::vector<int>& tp = plan_.tail_kslot_ptr;
-    if (plan_.nt > 0)
-        group(0, plan_.ntb * (plan_.ntb + 1) / 2, [&](int u) { return tp[u]; }, [&](int u) { return tp[u + 1]; },
-              nullptr);
-    else { ck_wide_.push_back(false); ck_kind_.push_back(0); }
-    ck_ptr_[plan_.nlevels + 1] = static_cast<int>(cu.size());
-    sp_ptr_[plan_.nlevels + 1] = static_cast<int>(su.size());
-    dck_u_.upload(cu, s);
-    dck_b_.upload(cb, s);
-    dck_e_.upload(ce, s);
-    dck_part_.upload(cp, s);
-    dsp_u_.upload(su, s);
-    dsp_p0_.upload(sp0, s);
-    dsp_n_.upload(sn, s);
-    dck_q_.upload(cq, s);
-    dSplitCnt_.alloc(std::max<size_t>(1, su.size()));
-    IPO_HIP_CHECK(hipMemsetAsync(dSplitCnt_.get(), 0, std::max<size_t>(1, su.size()) * sizeof(int), s));
-    dPartialTile_.alloc(std::max<size_t>(1, max_part) * (kTileRows * kTileRows + 4 * kTileRows));
+    GatherChunks g = ipo::build_gather_chunks(plan_, knobs_, h_.paths, vs);
+    dck_u_.upload(g.ck_u, s);
+    dck_b_.upload(g.ck_b, s);
+    dck_e_.upload(g.ck_e, s);
+    dck_part_.upload(g.ck_part, s);
+    dsp_u_.upload(g.sp_u, s);
+    dsp_p0_.upload(g.sp_p0, s);
+    dsp_n_.upload(g.sp_n, s);
+    dck_q_.upload(g.ck_q, s);
+    dSplitCnt_.alloc(g.split_cnt);
+    IPO_HIP_CHECK(hipMemsetAsync(dSplitCnt_.get(), 0, g.split_cnt * sizeof(int), s));
+    dPartialTile_.alloc(g.partial_tiles * (kTileRows * kTileRows + 4 * kTileRows));
     IPO_HIP_CHECK(hipStreamSynchronize(s));
+    h_.ck_ptr = std::move(g.ck_ptr);
+    h_.ck_kind = std::move(g.ck_kind);
+    h_.ck_wide = std::move(g.ck_wide);
 }
 
 // Launches per sweep and algorithmic work per phase occurrence
 void KktDevice::count_work() {
-    fwd_launches_ = bwd_launches_ = sf_level_ < plan_.nlevels ? 1 : 0;
-    for (int l = 0; l < sf_level_; l++) {
-        const int nsl = plan_.level_ptr[l + 1] - plan_.level_ptr[l];
-        const int nl = leaf_cnt_[l], n8 = leaf8_cnt_[l];
-        const int k = chunk_ptr_[l + 1] > chunk_ptr_[l] ? 2
-                    : (n8 > 0) + (nl > n8 && nsl > nl && knobs_.merge_levels ? 1 : (nl > n8) + (nsl > nl));
-        fwd_launches_ += k;
-        bwd_launches_ += k;
-    }
-    if (plan_.nt > 0) {
-        const int chain = plan_.ntb <= kChainMaxBlocks;
-        fwd_launches_ += 1 + (chain ? 1 : plan_.ntb);
-        bwd_launches_ += chain ? 1 : 1 + plan_.ntb;
-    }
-    const auto& P = plan_;
-    double gf = 0, gb = 0;
-    auto tasks_work = [&](const std::vector<TailTask>& ts) {
-        for (const TailTask& t : ts) {
-            const double ncd = P.col0[t.src + 1] - P.col0[t.src];
-            const double nr = __builtin_popcountll(t.rmask), ncl = __builtin_popcountll(t.cmask);
-            gf += 2.0 * ncd * nr * ncl;
-            gb += 8.0 * ncd * (nr + ncl);
-        }
-    };
-    tasks_work(P.utasks);
-    tasks_work(P.tail_tasks);
-    double df = 0, db = 0, tf = 0, tb = 0, sf = 0, sb = 0, lxs = 0;
-    for (int sp = 0; sp < P.nsup; sp++) {
-        const double nc = P.col0[sp + 1] - P.col0[sp], hb = P.rowptr[sp + 1] - P.rowptr[sp];
-        df += 2.0 * nc * nc * nc / 3.0;
-        db += 8.0 * 1.5 * nc * nc;
-        tf += hb * nc * nc;
-        tb += 16.0 * hb * nc;
-        lxs += (nc + hb) * nc;
-        gb += 16.0 * (nc + hb) * nc;      // read-modify-write of every target panel
-    }
-    const double sdf = df, sdb = db, stf = tf, stb = tb;     // sparse panels alone
-    for (int kb = 0; kb < P.ntb; kb++) {
-        const double nc = std::min(kPanelCols, P.nt - kb * kPanelCols), below = P.nt - kb * kPanelCols - nc;
-        df += 2.0 * nc * nc * nc / 3.0;
-        db += 8.0 * 1.5 * nc * nc;
-        tf += below * nc * nc;
-        tb += 16.0 * below * nc;                                // L21 read + write
-        const double nb = P.ntb - kb - 1;
-        sf += 2.0 * nc * (nb * (nb + 1) / 2) * kTileRows * kTileRows;
-        sb += (nb * (nb + 1) / 2) * (16.0 * kTileRows * kTileRows + 16.0 * kTileRows * nc);
-    }
-    gb += 16.0 * 0.5 * P.nt * P.nt;                                 // tail block read-modify-write
-    work_flops[kPhGather] = gf; work_bytes[kPhGather] = gb;
-    work_flops[kPhDiag] = df; work_bytes[kPhDiag] = db;
-    work_flops[kPhTrsm] = tf; work_bytes[kPhTrsm] = tb;
-    work_flops[kPhSyrk] = sf; work_bytes[kPhSyrk] = sb;
-    // Algorithmic flops per factorisation in SURVEY.md 8(d)'s unit: the
-    // reference's narth (ldlt.c:1243-1248), split by the phase doing each
-    // column's work (kkt_plan.h: narth_tail / narth_gather / narth_panel,
-    // which sum to narth).  What the kernels execute (plan flops above,
-    // the dense tail's explicit zeros) is not the work.  Bytes: each
-    // phase's entries of L read and written once (+ the gather's source
-    // reads from the plan).
-    (void)sdf; (void)stf; (void)df; (void)tf; (void)sf; (void)lxs;
-    work_flops[kPhGather] = P.narth_gather;
-    if (use_panel_) {   // k_panel_w does both: the diag phase carries the sparse trsm work;
-        // the dense tail is its own phase (k_tail_pr: panels + deferred
-        // trailing updates; its repair launches)
-        work_flops[kPhDiag] = P.narth_panel; work_bytes[kPhDiag] = sdb + stb;
-        work_flops[kPhTrsm] = work_bytes[kPhTrsm] = 0;
-        work_flops[kPhSyrk] = work_bytes[kPhSyrk] = 0;
-        work_flops[kPhTail] = P.narth_tail;
-        work_bytes[kPhTail] = 16.0 * (static_cast<double>(P.lnz_tail) + P.nt);
-    } else {            // per-phase path: the tail's work goes with its trailing updates
-        work_flops[kPhDiag] = P.narth_panel;
-        work_flops[kPhTrsm] = 0;
-        work_flops[kPhSyrk] = P.narth_tail;
-    }
-    // a sweep (s (4 nnz(L) + N) per iteration, a solve
-    // being one forward and one backward sweep): 2 nnz(L) + N / 2 flops,
-    // every entry of L read once (12 B with its index) and the vector
-    // values in and out
-    for (int ph : {kPhForward, kPhBackward}) {
-        work_flops[ph] = 2.0 * static_cast<double>(P.lnz) + 0.5 * T_;
-        work_bytes[ph] = 12.0 * static_cast<double>(P.lnz) + 16.0 * T_;
-    }
+    const WorkCounts w = ipo::count_work(plan_, knobs_, h_.chunk_ptr, h_.leaf_cnt, h_.leaf8_cnt, h_.sf_level);
+    h_.fwd_launches = w.fwd_launches;
+    h_.bwd_launches = w.bwd_launches;
+    std::copy(w.flops, w.flops + kNumPhases, work_flops);
+    std::copy(w.bytes, w.bytes + kNumPhases, work_bytes);
 }
 
 // Per-task source descriptors and per-slot records of the gather; kslot_v:
-// the sparse units' slots in visit order (build_gather_chunks)
+// the sparse units' slots in visit order (build_visit_slots)
 void KktDevice::build_slot_records(const std::vector<int>& kslot_v) {
     hipStream_t s = stream_;
     auto build = [&](const std::vector<TailTask>& ts, DevBuf<TaskSrc>& dst) {
-        std::vector<TaskSrc> v(ts.size());
-        for (size_t t = 0; t < ts.size(); t++) {
-            const int d = ts[t].src, ncd = plan_.col0[d + 1] - plan_.col0[d];
-            v[t].colbase = plan_.off[d] + ncd;
-            v[t].hd = ncd + (plan_.rowptr[d + 1] - plan_.rowptr[d]);
-            v[t].cd0 = plan_.col0[d];
-        }
+        const std::vector<TaskSrc> v = build_task_src(plan_, ts);
         dst.upload(v, s);
         IPO_HIP_CHECK(hipStreamSynchronize(s));
     };
     build(plan_.utasks, dusrc_);
     if (plan_.nt > 0) build(plan_.tail_tasks, dtsrc_);
-    // per k-slot records of the gather (SlotRec), expanded from the
-    // slot -> task -> source panel indirection
     auto expand = [&](const std::vector<int>& kslot, const std::vector<TailTask>& ts, DevBuf<SlotRec>& dst) {
-        std::vector<SlotRec> v(kslot.size());
-        for (size_t i = 0; i < kslot.size(); i++) {
-            const int sl = kslot[i];
-            SlotRec& r = v[i];
-            if (sl < 0) { r.rmask = r.cmask = 0; r.roff = 0; r.cdelta = 0; r.dk = 0; continue; }
-            const TailTask& t = ts[sl >> 6];
-            const int kl = sl & 63, d = t.src, ncd = plan_.col0[d + 1] - plan_.col0[d];
-            const int64_t hd = ncd + (plan_.rowptr[d + 1] - plan_.rowptr[d]);
-            r.rmask = t.rmask;
-            r.cmask = t.cmask;
-            r.roff = plan_.off[d] + ncd + kl * hd + t.rbase;
-            r.cdelta = t.cbase - t.rbase;
-            r.dk = plan_.col0[d] + kl;
-        }
+        const std::vector<SlotRec> v = ipo::build_slot_records(plan_, kslot, ts);
         dst.upload(v, s);
         IPO_HIP_CHECK(hipStreamSynchronize(s));
     };
-    expand(visits_ ? kslot_v : plan_.kslot, plan_.utasks, dslot_rec_);
+    expand(h_.paths.visits ? kslot_v : plan_.kslot, plan_.utasks, dslot_rec_);
     if (plan_.nt > 0) expand(plan_.tail_kslot, plan_.tail_tasks, dtail_slot_rec_);
     dutasks_.upload(reinterpret_cast<const uint64_t*>(plan_.utasks.data()), plan_.utasks.size() * 4, s);
 }
@@ -3648,32 +3319,27 @@ void KktDevice::setup_tail(int cus) {
         }
     }
     if (plan_.nt > 0 && plan_.ntb <= kTailSchedMaxBlocks) {
-        // look-ahead launches of at most one workgroup per CU (tail_visit_schedule)
+        TailSchedule ts = build_tail_schedule(plan_, knobs_, h_.paths, cus);
         if (knobs_.visit_sched) {
-            const std::vector<unsigned> vl =
-                tail_visit_schedule(plan_.ntb, plan_.nt, knobs_.visit_blocks, cus, knobs_.visit_xcd, visit_ptr_);
-            dvisit_list_.upload(vl, s);
-            IPO_HIP_CHECK(hipStreamSynchronize(s));   // vl is a local
+            dvisit_list_.upload(ts.visit_list, s);
+            IPO_HIP_CHECK(hipStreamSynchronize(s));   // ts is a local
+            h_.visit_ptr = std::move(ts.visit_ptr);
         }
-        // the persistent run (k_tail_run, default; its bails end in the same
-        // state as the per-step launches', so the repair and the sharded
-        // solve's per-phase redo are unchanged); the latest chunk of each
-        // column knobs_.visit_latest blocks
-        if (tail_run_) {
-            const std::vector<uint2> items =
-                tail_run_schedule(plan_.ntb, plan_.nt, knobs_.visit_blocks, knobs_.visit_latest, cus, run_ptr_);
-            drun_items_.upload(items, s);
+        if (h_.paths.tail_run) {
+            static_assert(sizeof(SchedUint2) == sizeof(uint2), "SchedUint2 is uploaded as uint2");
+            drun_items_.upload(reinterpret_cast<const uint2*>(ts.run_items.data()), ts.run_items.size(), s);
+            h_.run_ptr = std::move(ts.run_ptr);
             drun_cnt_.alloc(1 + plan_.ntb + static_cast<size_t>(plan_.ntb) * plan_.ntb + plan_.ntb);
             // each step's tile windows handed to the next step's pre-update as
             // they complete (kkt_dense.hip RunPub; off: the pre-update waits
             // for the whole previous step and reads S)
-            if (run_winpub_) {
+            if (h_.paths.run_winpub) {
                 drun_pub_.alloc(2 * static_cast<size_t>(plan_.ntb) * 4 * kTailPubWin);
                 drun_wflag_.alloc(static_cast<size_t>(plan_.ntb) * plan_.ntb * 4);
                 IPO_HIP_CHECK(hipMemsetAsync(drun_wflag_.get(), 0, drun_wflag_.bytes(), s));
                 run_epoch_ = 0;
             }
-            IPO_HIP_CHECK(hipStreamSynchronize(s));   // items is a local
+            IPO_HIP_CHECK(hipStreamSynchronize(s));   // ts is a local
         }
     }
 }
@@ -3710,120 +3376,44 @@ void KktDevice::alloc_numeric() {
     IPO_HIP_CHECK(hipStreamSynchronize(s));
 }
 
-// Sync-free top levels (k_fwd_sf / k_bwd_sf): from sf_level_ up every level
-// is at most kSfWidth supernodes wide (IPO_HIP_SF_WIDTH): 300 for factors
-// of fewer than 2^25 entries, 64 above.  Measured on one box: dfl001 64 /
-// 150 / 300 / 450 / 600 / all -> 290.9 / 292.5 / 292.7 / 292.7 / 292.1 /
-// 224.4 it/s (every level in the launch starves the wide bottom ones),
-// 25fv47 by intpt 932 -> 963 at 300; but banded configs[3] 76.9 -> 68.5 and
-// block-angular configs[4] 47.6 -> 39.3 at 300 (their upper levels hold
-// large chunked supernodes, which the per-level launches spread wider).  Their forward update values get
-// ybuf slices, and their z values zpad slices, of their own 128-B lines;
-// work items, per-supernode arrival counts and parents.  Called from the
-// constructor after the solve chunks are built; also uploads the forward
-// update lists (yrow_ptr as the plan's, yrow_idx with the moved slices).
-// cus: the device's CU count, the sweeps' grid.
-void KktDevice::build_sync_free_plan(int cus) {
-    const int kSfWidth = knobs_.sf_width > 0 ? knobs_.sf_width : plan_.lx_size < (int64_t(1) << 25) ? 300 : 64;
+// Sync-free top levels of the sweeps (kkt_schedule.h): the forward update
+// lists (yrow_ptr as the plan's, yrow_idx with the moved slices), the padded
+// slices, the items and their counters.  cus: the device's CU count, the
+// sweeps' grid.
+void KktDevice::build_sync_free_plan(const SolveChunks& ch, int cus) {
     hipStream_t s = stream_;
     dyrow_ptr_.upload(plan_.yrow_ptr, s);
-    const KktPlan& P = plan_;
-    const int ns = P.nsup;
-    sf_level_ = P.nlevels;
-    while (sf_level_ > 0 && P.level_ptr[sf_level_] - P.level_ptr[sf_level_ - 1] <= kSfWidth) sf_level_--;
-    if (P.nlevels - sf_level_ < 2) sf_level_ = P.nlevels;
-    if (!knobs_.sf) sf_level_ = P.nlevels;
-    auto chunked = [&](int sp) { const int l = P.level[sp]; return chunk_ptr_[l + 1] > chunk_ptr_[l]; };
-    auto nchunks = [&](int sp) { return (P.rowptr[sp + 1] - P.rowptr[sp] + 63) / 64; };
-    std::vector<int> ybase(ns + 1), zbase(ns, -1), zpi(T_ > 0 ? T_ : 1, -1), need(ns, 0), par(ns, -1);
-    size_t yend = P.rowptr.empty() ? 0 : P.rowptr.back(), zend = 0;
-    for (int sp = 0; sp < ns; sp++) {
-        if (P.level[sp] < sf_level_) { ybase[sp] = P.rowptr[sp]; continue; }
-        yend = (yend + 15) & ~size_t(15);
-        ybase[sp] = static_cast<int>(yend);
-        yend += P.rowptr[sp + 1] - P.rowptr[sp];
-        zend = (zend + 15) & ~size_t(15);
-        zbase[sp] = static_cast<int>(zend);
-        for (int c = P.col0[sp]; c < P.col0[sp + 1]; c++) zpi[c] = static_cast<int>(zend + c - P.col0[sp]);
-        zend += P.col0[sp + 1] - P.col0[sp];
-        const int pa = P.parent[sp];
-        if (pa >= 0) { par[sp] = pa; need[pa] += chunked(sp) ? nchunks(sp) : 1; }
-    }
-    ybase[ns] = static_cast<int>(yend);
-    std::vector<int> yidx(P.yrow_idx);
-    if (sf_level_ < P.nlevels) {       // update-value positions of the moved slices
-        std::vector<int> pos(yidx.empty() ? 1 : P.rowptr.back());
-        for (int sp = 0; sp < ns; sp++)
-            for (int i = P.rowptr[sp]; i < P.rowptr[sp + 1]; i++) pos[i] = ybase[sp] + (i - P.rowptr[sp]);
-        for (int& e : yidx) e = pos[e];
-    }
-    dyrow_idx_.upload(yidx, s);
-    dybase_.upload(ybase, s);
-    // Deep trees: the update values a narrow-range column receives from
-    // supernodes below the range (on configs[3] the 10^6 leaves and the wide
-    // levels: ~30 scattered values per row, ~5 us of the chain item's loads)
-    // are all known once the bottom levels are swept.  They are subtracted
-    // from the right-hand side by one pre-pass launch (k_fwd_pre: per column,
-    // in list order), and the sync-free items sum only the values of
-    // supernodes inside the range (their own lists, ylate_*).
-    pre_cols_ = 0;
-    if (visits_ && sf_level_ < P.nlevels) {
-        auto src_of = [&](int i) {        // the supernode whose row set holds R entry i
-            return static_cast<int>(std::upper_bound(P.rowptr.begin(), P.rowptr.end(), i) - P.rowptr.begin()) - 1;
-        };
-        std::vector<int> lptr(T_ + 1, 0), lidx, ecol, eptr{0}, eidx;
-        for (int v = 0; v < T_; v++) {
-            const int sv = v < P.tail_c0 ? P.sup_of[v] : -1;
-            const bool in_range = sv >= 0 && P.level[sv] >= sf_level_;
-            bool any_early = false;
-            // (columns outside the range keep empty late lists: only k_fwd_sf reads these)
-            for (int e = in_range ? P.yrow_ptr[v] : 0; e < (in_range ? P.yrow_ptr[v + 1] : 0); e++) {
-                const bool early = P.level[src_of(P.yrow_idx[e])] < sf_level_;
-                if (early) {
-                    if (!any_early) { ecol.push_back(v); any_early = true; }
-                    eidx.push_back(yidx[e]);
-                } else {
-                    lidx.push_back(yidx[e]);
-                }
-            }
-            if (any_early) eptr.push_back(static_cast<int>(eidx.size()));
-            lptr[v + 1] = static_cast<int>(lidx.size());
-        }
-        pre_cols_ = static_cast<int>(ecol.size());
-        dylate_ptr_.upload(lptr, s);
-        dylate_idx_.upload(lidx.empty() ? std::vector<int>{0} : lidx, s);
-        dpre_col_.upload(ecol.empty() ? std::vector<int>{0} : ecol, s);
-        dpre_ptr_.upload(eptr, s);
-        dpre_idx_.upload(eidx.empty() ? std::vector<int>{0} : eidx, s);
+    const SyncFreePlan sf = ipo::build_sync_free_plan(plan_, knobs_, h_.paths, ch);
+    const int ns = plan_.nsup;
+    h_.sf_level = sf.sf_level;
+    dyrow_idx_.upload(sf.yrow_idx, s);
+    dybase_.upload(sf.ybase, s);
+    h_.pre_cols = static_cast<int>(sf.pre_col.size());
+    if (sf.late_lists) {
+        dylate_ptr_.upload(sf.ylate_ptr, s);
+        dylate_idx_.upload(sf.ylate_idx.empty() ? std::vector<int>{0} : sf.ylate_idx, s);
+        dpre_col_.upload(sf.pre_col.empty() ? std::vector<int>{0} : sf.pre_col, s);
+        dpre_ptr_.upload(sf.pre_ptr, s);
+        dpre_idx_.upload(sf.pre_idx.empty() ? std::vector<int>{0} : sf.pre_idx, s);
         IPO_HIP_CHECK(hipStreamSynchronize(s));
     }
-    ybuf_stride_ = std::max<size_t>(yend, 1);
-    dYbuf_.alloc(2 * ybuf_stride_);
-    std::vector<int2> fi, bi;
-    for (int l = sf_level_; l < P.nlevels; l++)
-        for (int q = P.level_ptr[l]; q < P.level_ptr[l + 1]; q++) {
-            const int sp = P.level_sups[q];
-            if (!chunked(sp)) { fi.push_back(make_int2(sp, -1)); continue; }
-            for (int c = 0; c < nchunks(sp); c++) fi.push_back(make_int2(sp, h_chunk0_[sp] + c));
-        }
-    for (int l = P.nlevels - 1; l >= sf_level_; l--)
-        for (int q = P.level_ptr[l]; q < P.level_ptr[l + 1]; q++) {
-            const int sp = P.level_sups[q];
-            if (!chunked(sp)) { bi.push_back(make_int2(sp, -1)); continue; }
-            for (int c = 0; c < nchunks(sp); c++) bi.push_back(make_int2(sp, h_chunk0_[sp] + c));
-        }
-    nsf_f_ = static_cast<int>(fi.size());
-    nsf_b_ = static_cast<int>(bi.size());
-    if (sf_level_ < P.nlevels) {
-        dsf_items_f_.upload(fi, s);
-        h_sf_items_f_ = fi;
-        dsf_items_b_.upload(bi, s);
-        dsf_need_.upload(need, s);
-        dsf_par_.upload(par, s);
-        dsf_zbase_.upload(zbase, s);
-        dsf_zpi_.upload(zpi, s);
-        zpad_stride_ = std::max<size_t>(zend, 1);
-        dZpad_.alloc(2 * zpad_stride_);
+    h_.ybuf_stride = sf.ybuf_stride;
+    dYbuf_.alloc(2 * h_.ybuf_stride);
+    h_.nsf_f = static_cast<int>(sf.items_f.size());
+    h_.nsf_b = static_cast<int>(sf.items_b.size());
+    if (sf.range(plan_)) {
+        static_assert(sizeof(SchedInt2) == sizeof(int2), "SchedInt2 is uploaded as int2");
+        dsf_items_f_.upload(reinterpret_cast<const int2*>(sf.items_f.data()), sf.items_f.size(), s);
+#ifdef IPO_SF_STAMPS
+        h_sf_items_f_ = sf.items_f;
+#endif
+        dsf_items_b_.upload(reinterpret_cast<const int2*>(sf.items_b.data()), sf.items_b.size(), s);
+        dsf_need_.upload(sf.need, s);
+        dsf_par_.upload(sf.par, s);
+        dsf_zbase_.upload(sf.zbase, s);
+        dsf_zpi_.upload(sf.zpi, s);
+        h_.zpad_stride = sf.zpad_stride;
+        dZpad_.alloc(2 * h_.zpad_stride);
         for (DevBuf<int>* b : {&dsf_fcnt_, &dsf_fflag_, &dsf_bcnt_, &dsf_bflag_}) {
             b->alloc(ns);
             IPO_HIP_CHECK(hipMemsetAsync(b->get(), 0, ns * sizeof(int), s));
@@ -3836,14 +3426,14 @@ void KktDevice::build_sync_free_plan(int cus) {
                               reinterpret_cast<const void*>(&k_bwd_sf<1>), reinterpret_cast<const void*>(&k_bwd_sf<2>)})
             IPO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kChainLds));
     }
-    IPO_HIP_CHECK(hipStreamSynchronize(s));   // the host vectors above are locals
+    IPO_HIP_CHECK(hipStreamSynchronize(s));   // sf is a local
 }
 
 #ifdef IPO_SF_STAMPS
 // Per-level summary of the last forward sync-free sweep's stamps (10 ns
 // ticks): items, mean wait / diag (gather + L11 solve) / rest / hand-off,
 // and when the level's last item finished.
-static void dump_sf_stamps(const std::vector<int2>& items, const KktPlan& P, const std::string& file) {
+static void dump_sf_stamps(const std::vector<SchedInt2>& items, const KktPlan& P, const std::string& file) {
     std::vector<long long> st((size_t)(1 << 15) * 10);
     if (hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(g_sfst), st.size() * sizeof(long long)) != hipSuccess) return;
     const int n = std::min<int>(items.size(), 1 << 15);
@@ -3892,33 +3482,22 @@ KktDevice::~KktDevice() {
     for (hipEvent_t e : kev_) (void)hipEventDestroy(e);
 }
 
-static PlanView make_view(const KktPlan&, const DevBuf<int>& col0, const DevBuf<int>& rowptr, const DevBuf<int>& rows,
-                          const DevBuf<int64_t>& off, const DevBuf<int>& us, const DevBuf<int>& ut,
-                          const DevBuf<int>& tp, const DevBuf<int>& tq, const DevBuf<int>& t0, const DevBuf<int>& t1,
-                          const DevBuf<int>& src, const DevBuf<int>& r0, const DevBuf<int>& r1,
-                          const DevBuf<int64_t>& relptr, const DevBuf<int>& rel, const DevBuf<double>& lx,
-                          const DevBuf<double>& dg, const DevBuf<int>& live, const DevBuf<int>& flags) {
+PlanView KktDevice::plan_view() const {
     PlanView v;
-    v.col0 = col0.get(); v.rowptr = rowptr.get(); v.rows = rows.get(); v.off = off.get();
-    v.unit_sup = us.get(); v.unit_tile = ut.get(); v.task_ptr = tp.get(); v.task_pair = tq.get();
-    v.task_i0 = t0.get(); v.task_i1 = t1.get(); v.upd_src = src.get(); v.upd_r0 = r0.get(); v.upd_r1 = r1.get();
-    v.relptr = relptr.get(); v.rel = rel.get(); v.Lx = lx.get(); v.dg = dg.get(); v.live = live.get();
-    v.flags = flags.get();
-    v.sign = flags.get() + 4;
-    return v;
-}
-
-#define IPO_VIEW() with_scale(make_view(plan_, dcol0_, drowptr_, drows_, doff_, dunit_sup_, dunit_tile_, dtask_ptr_, \
-                             dtask_pair_, dtask_i0_, dtask_i1_, dupd_src_, dupd_r0_, dupd_r1_, drelptr_, drel_, \
-                             dLx_, dDg_, dLive_, dFlags_), dDscale_.get(), pivot_tol_, dIncons_.get(), \
-                             dybase_.get(), knobs_.update_xcd)
-
-static PlanView with_scale(PlanView v, double* dscale, double tau, int* incons, const int* ybase, int xcd) {
-    v.xcd = xcd;     // gather launches of at least this many chunks walk them XCD by XCD (0: off)
-    v.dscale = dscale;
-    v.tau = tau;
-    v.incons = incons;
-    v.ybase = ybase;
+    v.col0 = dcol0_.get(); v.rowptr = drowptr_.get(); v.rows = drows_.get(); v.off = doff_.get();
+    v.unit_sup = dunit_sup_.get(); v.unit_tile = dunit_tile_.get();
+    v.task_ptr = dtask_ptr_.get(); v.task_pair = dtask_pair_.get();
+    v.task_i0 = dtask_i0_.get(); v.task_i1 = dtask_i1_.get();
+    v.upd_src = dupd_src_.get(); v.upd_r0 = dupd_r0_.get(); v.upd_r1 = dupd_r1_.get();
+    v.relptr = drelptr_.get(); v.rel = drel_.get();
+    v.Lx = dLx_.get(); v.dg = dDg_.get(); v.live = dLive_.get();
+    v.flags = dFlags_.get();
+    v.sign = dFlags_.get() + 4;
+    v.xcd = knobs_.update_xcd;     // gather launches of at least this many chunks walk them XCD by XCD (0: off)
+    v.dscale = dDscale_.get();
+    v.tau = pivot_tol_;
+    v.incons = dIncons_.get();
+    v.ybase = dybase_.get();
     return v;
 }
 
@@ -3932,9 +3511,9 @@ TailView KktDevice::tail_view() const {
     t.tasks = reinterpret_cast<const TailTask*>(dtail_tasks_.get());
     t.W = dW_.get();
     t.vk = knobs_.visit_blocks;
-    if (!visit_ptr_.empty()) {
+    if (!h_.visit_ptr.empty()) {
         t.vlist = dvisit_list_.get();
-        t.vptr = visit_ptr_.data();
+        t.vptr = h_.visit_ptr.data();
     }
     // dependent pivots in the look-ahead panel: its failed checks fall back on
     // the host repair, which the sharded solve does not use
@@ -4023,7 +3602,7 @@ void KktDevice::factor_core(const double* dE, const double* dD) {
 bool KktDevice::factor_pass(const double* dE, const double* dD, bool fused, bool tail_fused) {
     hipStream_t s = stream_;
     if (timing_) IPO_HIP_CHECK(hipEventRecord(ev0_, s));
-    const PlanView pv = IPO_VIEW();
+    const PlanView pv = plan_view();
     const int nz = static_cast<int>(plan_.amap.size());
     if (plan_.nt > 0 && !xch_) {
         // the sparse panels, then the tail's lower block triangle only (the
@@ -4047,7 +3626,7 @@ bool KktDevice::factor_pass(const double* dE, const double* dD, bool fused, bool
         // shards: S = sum of every shard's assembled + gathered tail (exchange.h)
         xsum(tv.S, static_cast<size_t>(plan_.nt) * plan_.nt, RedOp::Sum);
         xsum(dDscale_.get() + plan_.tail_c0, plan_.nt, RedOp::Sum);
-        if (tail_fused && tail_run_) {     // one persistent launch (kkt_dense.hip, k_tail_run)
+        if (tail_fused && h_.paths.tail_run) {     // one persistent launch (kkt_dense.hip, k_tail_run)
             launch_tail_from(0, true);
         } else if (tail_fused) {     // look-ahead steps (kkt_dense.hip, k_tail_pr)
             // one event pair around the steps (a pair per launch added its
@@ -4094,21 +3673,21 @@ void KktDevice::enqueue_levels(const PlanView& pv, const TailView& tv, bool fuse
         }
         const int q0 = plan_.level_ptr[l], q1 = plan_.level_ptr[l + 1];
         ph_begin(s);
-        if (fused && split_level_[l]) {
+        if (fused && h_.split_level[l]) {
             launch_diag(pv, dlevel_sups_.get(), q0, q1 - q0, tv, 0, s);
             launch_trsm(pv, u0, u1 - u0, tv, 0, s);
             ph_end(kPhDiag, 2, s);
         } else if (fused) {
-            const int nsm = small_ptr_[l + 1] - small_ptr_[l], nfu = fu_ptr_[l + 1] - fu_ptr_[l];
-            const int n1 = small1_cnt_[l];
+            const int nsm = h_.small_ptr[l + 1] - h_.small_ptr[l], nfu = h_.fu_ptr[l + 1] - h_.fu_ptr[l];
+            const int n1 = h_.small1_cnt[l];
             if (knobs_.merge_levels && nfu > 0 && nsm > n1) {
-                launch_panel_small(pv, dsmall_sups_.get(), small_ptr_[l], n1, tv.sdep, s, n1);
-                launch_panel_ws(pv, dfu_sup_.get(), dfu_j_.get(), fu_ptr_[l], nfu, tv, dsmall_sups_.get(),
-                                small_ptr_[l] + n1, nsm - n1, tv.sdep, s);
+                launch_panel_small(pv, dsmall_sups_.get(), h_.small_ptr[l], n1, tv.sdep, s, n1);
+                launch_panel_ws(pv, dfu_sup_.get(), dfu_j_.get(), h_.fu_ptr[l], nfu, tv, dsmall_sups_.get(),
+                                h_.small_ptr[l] + n1, nsm - n1, tv.sdep, s);
                 ph_end(kPhDiag, 1 + (n1 > 0), s);
             } else {
-                launch_panel_small(pv, dsmall_sups_.get(), small_ptr_[l], nsm, tv.sdep, s, n1);
-                launch_panel(pv, dfu_sup_.get(), dfu_j_.get(), fu_ptr_[l], nfu, tv, -1, s);
+                launch_panel_small(pv, dsmall_sups_.get(), h_.small_ptr[l], nsm, tv.sdep, s, n1);
+                launch_panel(pv, dfu_sup_.get(), dfu_j_.get(), h_.fu_ptr[l], nfu, tv, -1, s);
                 ph_end(kPhDiag, (nsm > 0) + (nfu > 0), s);
             }
         } else {
@@ -4185,17 +3764,17 @@ bool KktDevice::finish_pass(bool fused) {
 // exactly the items of launches <= tb (later items were skipped uncounted).
 void KktDevice::launch_tail_from(int t0, bool reset) {
     hipStream_t s = stream_;
-    const PlanView pv = IPO_VIEW();
+    const PlanView pv = plan_view();
     const size_t ncnt = reset ? drun_cnt_.size() : 1;
     IPO_HIP_CHECK(hipMemsetAsync(drun_cnt_.get(), 0, ncnt * sizeof(int), s));
     TailRun rc;
-    rc.items = drun_items_.get() + run_ptr_[t0];
-    rc.n = run_ptr_[plan_.ntb] - run_ptr_[t0];
+    rc.items = drun_items_.get() + h_.run_ptr[t0];
+    rc.n = h_.run_ptr[plan_.ntb] - h_.run_ptr[t0];
     rc.t0 = t0;
     rc.ticket = drun_cnt_.get();
     rc.pdone = drun_cnt_.get() + 1;
     rc.vseq = drun_cnt_.get() + 1 + plan_.ntb;
-    if (run_winpub_) {
+    if (h_.paths.run_winpub) {
         if (run_epoch_ == INT_MAX) {      // (never within a process's life: one epoch per factorisation)
             IPO_HIP_CHECK(hipMemsetAsync(drun_wflag_.get(), 0, drun_wflag_.bytes(), s));
             run_epoch_ = 0;
@@ -4223,7 +3802,7 @@ void KktDevice::launch_tail_from(int t0, bool reset) {
 // Repeats while a later column bails.
 void KktDevice::repair_tail() {
     hipStream_t s = stream_;
-    const PlanView pv = IPO_VIEW();
+    const PlanView pv = plan_view();
     for (;;) {
         const int tb = hFlags_[4] - 1;
         tm_.tail_repairs++;
@@ -4253,7 +3832,7 @@ void KktDevice::repair_tail() {
             tm_.tail_dep_rounds += kDepBatch;
             if (hFlags_[6]) break;
         }
-        if (tail_run_) {
+        if (h_.paths.tail_run) {
             launch_tail_from(tb + 1, false);
         } else {
             ph_begin(s);
@@ -4269,7 +3848,7 @@ void KktDevice::repair_tail() {
 // Gather launch of one level (tail < 0) or of the dense tail (group =
 // nlevels): every chunk; split units combined by their last-arriving chunk.
 int KktDevice::launch_gather(const PlanView& pv, const TailView& tv, int tail, int group, hipStream_t s) {
-    const int c0 = ck_ptr_[group], c1 = ck_ptr_[group + 1];
+    const int c0 = h_.ck_ptr[group], c1 = h_.ck_ptr[group + 1];
     if (c1 <= c0) return 0;
     const SlotRec* recs = tail < 0 ? dslot_rec_.get() : dtail_slot_rec_.get();
     // groups whose split units have many chunks sum their partials four
@@ -4278,18 +3857,18 @@ int KktDevice::launch_gather(const PlanView& pv, const TailView& tv, int tail, i
     // developer stamps (IPO_HIP_GATHER_STAMPS=<group>): per workgroup
     // s_memrealtime at start / records / values / MFMA / put / stores
     long long* stq = nullptr;
-    if (gst_group_ == group && tail < 0 && ck_kind_[group] > 0) {
+    if (gst_group_ == group && tail < 0 && h_.ck_kind[group] > 0) {
         if (!dGStamp_.get()) dGStamp_.alloc(1024 * 8);
         stq = dGStamp_.get();
         gst_n_ = c1 - c0;
     }
-    if (ck_kind_[group] == 2) {
+    if (h_.ck_kind[group] == 2) {
         hipLaunchKernelGGL(k_update_quad, dim3(c1 - c0), dim3(NT), 0, s, pv, tv, recs, dck_u_.get(), dck_b_.get(),
                            dck_e_.get(), dck_part_.get(), c0, stq);
         return 1;
     }
-    if (ck_kind_[group] == 1) {
-        if (ck_wide_[group])
+    if (h_.ck_kind[group] == 1) {
+        if (h_.ck_wide[group])
         hipLaunchKernelGGL(k_update_flat<4>, dim3(c1 - c0), dim3(NT), 0, s, pv, tv, tail, recs, dck_u_.get(),
                            dck_b_.get(), dck_e_.get(), dck_part_.get(), c0, dPartialTile_.get(), dck_q_.get(),
                            dsp_p0_.get(), dsp_n_.get(), dSplitCnt_.get(), stq);
@@ -4305,7 +3884,7 @@ int KktDevice::launch_gather(const PlanView& pv, const TailView& tv, int tail, i
                            dck_e_.get(), dck_part_.get(), c0, dPartialTile_.get(), dck_q_.get(), dsp_p0_.get(),
                            dsp_n_.get(), dSplitCnt_.get());
     };
-    if (ck_wide_[group]) {
+    if (h_.ck_wide[group]) {
         // (four partials in flight spill at 128 and at 168 VGPRs; 3 per CU
         // with 16 spilled measured no faster than 2 per CU)
         go(k_update<4, 1>);
@@ -4353,21 +3932,21 @@ void KktDevice::ph_collect() {
 template <int R>
 void KktDevice::sweep(double* dz, const double* epsp) {
     hipStream_t s = stream_;
-    const PlanView pv = IPO_VIEW();
-    const SweepVecs V{dz, static_cast<size_t>(T_), dYbuf_.get(), ybuf_stride_};
-    const size_t ps = partial_stride_;
+    const PlanView pv = plan_view();
+    const SweepVecs V{dz, static_cast<size_t>(T_), dYbuf_.get(), h_.ybuf_stride};
+    const size_t ps = h_.partial_stride;
     if (timing_) IPO_HIP_CHECK(hipEventRecord(ev2_, s));
     ph_begin(s);
-    for (int l = 0; l < sf_level_; l++) {
+    for (int l = 0; l < h_.sf_level; l++) {
         const int q0 = plan_.level_ptr[l], q1 = plan_.level_ptr[l + 1];
-        const int cb = chunk_ptr_[l], ce = chunk_ptr_[l + 1];
+        const int cb = h_.chunk_ptr[l], ce = h_.chunk_ptr[l + 1];
         if (ce > cb) {
             hipLaunchKernelGGL(k_fwd_diag<R>, dim3(q1 - q0), dim3(NT), 0, s, pv, dlevel_sups_.get(), q0,
                                dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
             hipLaunchKernelGGL(k_fwd_gemv<R>, dim3(ce - cb), dim3(NT), 0, s, pv, dchunk_sup_.get(), dchunk_r0_.get(), cb,
                                V);
         } else {
-            const int nl = leaf_cnt_[l], n8 = leaf8_cnt_[l];
+            const int nl = h_.leaf_cnt[l], n8 = h_.leaf8_cnt[l];
             if (n8 > 0)
                 hipLaunchKernelGGL(k_fwd_leaf8<R>, dim3(ceil_div(n8, NT / kSmallLeaf)), dim3(NT), 0, s, pv,
                                    dsweep_sups_.get(), q0, n8, dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
@@ -4386,15 +3965,15 @@ void KktDevice::sweep(double* dz, const double* epsp) {
             }
         }
     }
-    if (sf_level_ < plan_.nlevels) {      // the narrow top levels in one launch
-        const SfView sf{dsf_items_f_.get(), nsf_f_, dsf_fcnt_.get(), dsf_fflag_.get(), dsf_need_.get(), dsf_par_.get(),
-                        dsf_zbase_.get(), dsf_zpi_.get(), dZpad_.get(), zpad_stride_, ++sf_fwd_epoch_,
-                        dsf_ticket_.get(), sf_tbase(0, nsf_f_)};
-        const bool pre = pre_cols_ > 0 || dylate_ptr_.get();
-        if (pre_cols_ > 0)
-            hipLaunchKernelGGL(k_fwd_pre<R>, dim3(ceil_div(pre_cols_, NT)), dim3(NT), 0, s, pre_cols_, dpre_col_.get(),
+    if (h_.sf_level < plan_.nlevels) {      // the narrow top levels in one launch
+        const SfView sf{dsf_items_f_.get(), h_.nsf_f, dsf_fcnt_.get(), dsf_fflag_.get(), dsf_need_.get(), dsf_par_.get(),
+                        dsf_zbase_.get(), dsf_zpi_.get(), dZpad_.get(), h_.zpad_stride, ++sf_fwd_epoch_,
+                        dsf_ticket_.get(), sf_tbase(0, h_.nsf_f)};
+        const bool pre = h_.pre_cols > 0 || dylate_ptr_.get();
+        if (h_.pre_cols > 0)
+            hipLaunchKernelGGL(k_fwd_pre<R>, dim3(ceil_div(h_.pre_cols, NT)), dim3(NT), 0, s, h_.pre_cols, dpre_col_.get(),
                                dpre_ptr_.get(), dpre_idx_.get(), V);
-        hipLaunchKernelGGL(k_fwd_sf<R>, dim3(std::min(sf_grid_, nsf_f_)), dim3(NT), kChainLds, s, pv, sf,
+        hipLaunchKernelGGL(k_fwd_sf<R>, dim3(std::min(sf_grid_, h_.nsf_f)), dim3(NT), kChainLds, s, pv, sf,
                            pre ? dylate_ptr_.get() : dyrow_ptr_.get(), pre ? dylate_idx_.get() : dyrow_idx_.get(),
                            dchunk_r0_.get(), V, epsp);
     }
@@ -4404,7 +3983,7 @@ void KktDevice::sweep(double* dz, const double* epsp) {
         hipLaunchKernelGGL(k_tail_gather<R>, dim3(ceil_div(plan_.nt, 4)), dim3(NT), 0, s, tv, dyrow_ptr_.get(),
                            dyrow_idx_.get(), V);
         tail_rhs_end(dz, R);
-        if (chain_lead_) {
+        if (h_.paths.chain_lead) {
             const int grid = 1 + std::max(0, plan_.ntb - 1 - kLeadBlocks);
             if (lead_ticket_next_ + grid > (1LL << 30)) {
                 IPO_HIP_CHECK(hipMemsetAsync(dlead_ticket_.get(), 0, sizeof(int), s));
@@ -4422,7 +4001,7 @@ void KktDevice::sweep(double* dz, const double* epsp) {
             hipLaunchKernelGGL(k_tail_fwd_chain<R>, dim3(plan_.ntb), dim3(NT), kChainLds, s, pv, tv, V, epsp,
                                dChainGran_.get(), ++chain_epoch_);
 #ifdef IPO_LEAD_STAMPS
-        if (chain_lead_ && chain_epoch_ % 64 == 41) {
+        if (h_.paths.chain_lead && chain_epoch_ % 64 == 41) {
             double st[8][4];
             IPO_HIP_CHECK(hipStreamSynchronize(s));
             IPO_HIP_CHECK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_lead_stats), sizeof(st)));
@@ -4434,7 +4013,7 @@ void KktDevice::sweep(double* dz, const double* epsp) {
         }
 #endif
     }
-    ph_end(kPhForward, fwd_launches_, s);
+    ph_end(kPhForward, h_.fwd_launches, s);
     ph_begin(s);
     if (plan_.nt > 0) {
         const TailView tv = tail_view();
@@ -4445,23 +4024,23 @@ void KktDevice::sweep(double* dz, const double* epsp) {
             hipLaunchKernelGGL(k_tail_bwd_chain<R>, dim3(plan_.ntb), dim3(NT), kChainLds, s, pv, tv, V, epsp,
                                dChainGran_.get(), ++chain_epoch_);
     }
-    if (sf_level_ < plan_.nlevels) {
-        const SfView sf{dsf_items_b_.get(), nsf_b_, dsf_bcnt_.get(), dsf_bflag_.get(), dsf_need_.get(), dsf_par_.get(),
-                        dsf_zbase_.get(), dsf_zpi_.get(), dZpad_.get(), zpad_stride_, ++sf_bwd_epoch_,
-                        dsf_ticket_.get() + 1, sf_tbase(1, nsf_b_)};
-        hipLaunchKernelGGL(k_bwd_sf<R>, dim3(std::min(sf_grid_, nsf_b_)), dim3(NT), kChainLds, s, pv, sf,
+    if (h_.sf_level < plan_.nlevels) {
+        const SfView sf{dsf_items_b_.get(), h_.nsf_b, dsf_bcnt_.get(), dsf_bflag_.get(), dsf_need_.get(), dsf_par_.get(),
+                        dsf_zbase_.get(), dsf_zpi_.get(), dZpad_.get(), h_.zpad_stride, ++sf_bwd_epoch_,
+                        dsf_ticket_.get() + 1, sf_tbase(1, h_.nsf_b)};
+        hipLaunchKernelGGL(k_bwd_sf<R>, dim3(std::min(sf_grid_, h_.nsf_b)), dim3(NT), kChainLds, s, pv, sf,
                            dchunk_r0_.get(), dsup_chunk0_.get(), dPartial_.get(), ps, V, epsp);
     }
-    for (int l = sf_level_ - 1; l >= 0; l--) {
+    for (int l = h_.sf_level - 1; l >= 0; l--) {
         const int q0 = plan_.level_ptr[l], q1 = plan_.level_ptr[l + 1];
-        const int cb = chunk_ptr_[l], ce = chunk_ptr_[l + 1];
+        const int cb = h_.chunk_ptr[l], ce = h_.chunk_ptr[l + 1];
         if (ce > cb) {
             hipLaunchKernelGGL(k_bwd_partial<R>, dim3(ce - cb), dim3(NT), 0, s, pv, dchunk_sup_.get(), dchunk_r0_.get(),
                                cb, V, dPartial_.get(), ps);
             hipLaunchKernelGGL(k_bwd_finish<R>, dim3(q1 - q0), dim3(NT), 0, s, pv, dlevel_sups_.get(), q0,
                                dsup_chunk0_.get(), dPartial_.get(), ps, V, epsp);
         } else {
-            const int nl = leaf_cnt_[l], n8 = leaf8_cnt_[l];
+            const int nl = h_.leaf_cnt[l], n8 = h_.leaf8_cnt[l];
             if (n8 > 0)
                 hipLaunchKernelGGL(k_bwd_leaf8<R>, dim3(ceil_div(n8, NT / kSmallLeaf)), dim3(NT), 0, s, pv,
                                    dsweep_sups_.get(), q0, n8, V, epsp);
@@ -4479,7 +4058,7 @@ void KktDevice::sweep(double* dz, const double* epsp) {
             }
         }
     }
-    ph_end(kPhBackward, bwd_launches_, s);
+    ph_end(kPhBackward, h_.bwd_launches, s);
     IPO_HIP_CHECK(hipGetLastError());
     if (timing_) {
         IPO_HIP_CHECK(hipEventRecord(ev3_, s));
@@ -4511,12 +4090,12 @@ int KktDevice::sf_tbase(int d, int nitems) {
 // one right-hand side, per-block launches.
 void KktDevice::sweep_blocked(double* dz, const double* epsp) {
     hipStream_t s = stream_;
-    const PlanView pv = IPO_VIEW();
-    const SweepVecs V{dz, static_cast<size_t>(T_), dYbuf_.get(), ybuf_stride_};
-    const size_t ps = partial_stride_;
+    const PlanView pv = plan_view();
+    const SweepVecs V{dz, static_cast<size_t>(T_), dYbuf_.get(), h_.ybuf_stride};
+    const size_t ps = h_.partial_stride;
     for (int l = 0; l < plan_.nlevels; l++) {
         const int q0 = plan_.level_ptr[l], q1 = plan_.level_ptr[l + 1];
-        const int cb = chunk_ptr_[l], ce = chunk_ptr_[l + 1];
+        const int cb = h_.chunk_ptr[l], ce = h_.chunk_ptr[l + 1];
         if (ce > cb) {
             hipLaunchKernelGGL(k_fwd_diag<1>, dim3(q1 - q0), dim3(NT), 0, s, pv, dlevel_sups_.get(), q0,
                                dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
@@ -4544,7 +4123,7 @@ void KktDevice::sweep_blocked(double* dz, const double* epsp) {
     }
     for (int l = plan_.nlevels - 1; l >= 0; l--) {
         const int q0 = plan_.level_ptr[l], q1 = plan_.level_ptr[l + 1];
-        const int cb = chunk_ptr_[l], ce = chunk_ptr_[l + 1];
+        const int cb = h_.chunk_ptr[l], ce = h_.chunk_ptr[l + 1];
         if (ce > cb) {
             hipLaunchKernelGGL(k_bwd_partial<1>, dim3(ce - cb), dim3(NT), 0, s, pv, dchunk_sup_.get(), dchunk_r0_.get(),
                                cb, V, dPartial_.get(), ps);

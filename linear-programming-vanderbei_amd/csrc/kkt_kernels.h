@@ -1,7 +1,8 @@
 // kkt_kernels.h -- what the KKT kernel translation units share: the device
 // view of the symbolic plan and the launchers of the dense per-panel kernels
 // (kkt_dense.hip), which live in their own translation unit because their
-// fully unrolled register code dominates compile time.
+// fully unrolled register code dominates compile time.  (The dense tail's
+// host schedules: kkt_schedule.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -102,23 +103,8 @@ void launch_panel(const PlanView& pv, const int* fu_sup, const int* fu_j, int f0
 // the deferred trailing updates ("visits") scheduled for launch t -- one
 // launch per block column.  W = L21 D is formed from L and D where used.
 void launch_tail_step(const PlanView& pv, const TailView& tv, int t, hipStream_t s);
-// visit tiles of launch t (tail of ntb block columns, chunks of K blocks)
-int tail_visit_tiles(int ntb, int t, int K);
-// The visits of every look-ahead launch placed so that no launch needs more
-// than `cap` workgroups (one round on `cap` CUs): visit_hi's chunks, with
-// tiles' first chunks moved into earlier launches where a launch would
-// overflow.  xcd: a column's visits grouped on one XCD within each launch.
-// Returns the list (TailView::vlist layout) and ptr[0..ntb].
-std::vector<unsigned> tail_visit_schedule(int ntb, int nt, int K, int cap, bool xcd, std::vector<int>& ptr);
-// Items per launch t (ptr[t] .. ptr[t + 1]): panel workgroups (j, t | chunks
-// of column t << 8 | 1 << 31), then visits (bi | c << 8 | b0 << 16 | b1 << 24,
-// t | chunk index << 8), column t + 1's first.  Column c's chunks: the latest
-// L blocks before c - 1 in launch c - 1, then K at a time in launches c - 2,
-// ...; launches over `cap` items move first chunks earlier.
-std::vector<uint2> tail_run_schedule(int ntb, int nt, int K, int L, int cap, std::vector<int>& ptr);
+// The items of tail_run_schedule (kkt_schedule.h) from rc.t0 on, one persistent launch.
 void launch_tail_run(const PlanView& pv, const TailView& tv, const TailRun& rc, hipStream_t s);
-// algorithmic flops / bytes of every visit of one factorisation
-void tail_visit_work(int ntb, int nt, int K, double& flops, double& bytes);
 // Repair path, block column kb of the dense tail with the dependent-pivot
 // rule: one round (k_tail_dep); sti = two copies of {k0, 1 + pending column,
 // done, ndep}, both zeroed before round 0; round r reads copy r & 1 and

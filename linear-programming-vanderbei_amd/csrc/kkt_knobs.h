@@ -14,7 +14,7 @@
 
 namespace ipo {
 
-// Blocks per visit of the look-ahead dense tail (kkt_dense.hip, visit_hi).
+// Blocks per visit of the look-ahead dense tail (kkt_schedule.h, visit_hi).
 // Measured on dfl001's tail (tools/ubench_tail): per-step launches (round 4)
 // 4 -> 2.43 ms, 6 -> 2.26, 8 -> 2.55; the persistent run with the window
 // hand-off (round 6, latest chunk L in brackets) 3 -> 1.92 (3), 4 -> 1.79
@@ -102,7 +102,7 @@ struct KktKnobs {
     // IPO_HIP_GATHER_QUAD (default 1; 0 off): quadrant gathers (k_update_quad)
     // on the narrow levels of deep trees
     bool gather_quad = true;
-    // IPO_HIP_SMALL_LEAVES (unset (-1): kSmallLeafMinCount, kkt_device.hip;
+    // IPO_HIP_SMALL_LEAVES (unset (-1): kSmallLeafMinCount, kkt_schedule.h;
     // else max(0, v); 0 never): levels with at least this many small leaves
     // sweep them eight to a wave (k_fwd_leaf8 / k_bwd_leaf8), and levels with
     // at least this many single-column small panels of <= 8 rows factor them
@@ -144,7 +144,7 @@ struct KktKnobs {
     int min_chunk = 64;
     // IPO_HIP_SF_WIDTH (unset (-1): 300 for factors of fewer than 2^25
     // entries, 64 above; else max(1, v)): the sync-free range holds the top
-    // levels of at most this many supernodes (build_sync_free_plan)
+    // levels of at most this many supernodes (kkt_paths, kkt_schedule.cpp)
     int sf_width = -1;
     // IPO_HIP_UPDATE_XCD (default 1024; max(0, v); 0 off): PlanView::xcd --
     // gather launches of at least this many chunks walk them XCD by XCD

@@ -121,7 +121,7 @@ struct SlotRec {
 };
 
 constexpr int kMaxChunkSlots = 512;   // largest split-K chunk of the gather
-constexpr int kVisitLevels = 256;     // trees at least this deep gather early slots as visits (kkt_device.hip)
+constexpr int kVisitLevels = 256;     // trees at least this deep gather early slots as visits (kkt_schedule.cpp)
 constexpr int kVisitSlots = 64;       // slots per visit
 constexpr int kFlatMaxChunks = 2048;
 constexpr int kQuadMaxUnits = 512;    // quadrant gathers for deep-tree launches of at most this many units / visits

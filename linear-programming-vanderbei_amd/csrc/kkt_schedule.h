@@ -1,0 +1,210 @@
+// kkt_schedule.h -- the launch schedule of a KktDevice as host-only code:
+// what the constructor derives from the symbolic plan, the runtime knobs and
+// the device's CU count before it uploads anything.  Pure functions, one per
+// constructor step, each returning the arrays that step uploads and the few
+// counts and flags the launch code reads on the host (KktLaunch).  No HIP, no
+// environment: the unit builds with a plain C++17 compiler, so the ordering
+// properties the persistent kernels rely on (an item waits only on items
+// earlier in its list) are tested on the CPU (tests/test_kkt_schedule.py,
+// tests/test_tail_schedule.py).  The dense tail's host schedules live here
+// too.  build_kkt_schedule runs every part in the constructor's order.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "kkt_knobs.h"
+#include "kkt_plan.h"
+
+namespace ipo {
+
+constexpr int kSmallLeaf = 8;                  // rows and update values of a small leaf (k_fwd_leaf8 / k_bwd_leaf8)
+constexpr int kSmallLeafMinCount = 32768;      // per level, else one wave per leaf
+constexpr int kChunkRows = 128;                // a level with a panel of more rows below is solved in 64-row chunks
+// the dense-tail sweep chains keep one workgroup per block resident
+constexpr int kChainMaxBlocks = 200;
+// most block columns of a scheduled tail: the schedules pack block indices
+// and chunk counts into 8 bits each (tail_visit_schedule, tail_run_schedule);
+// a larger tail takes the per-step launches with the visit_hi formula
+constexpr int kTailSchedMaxBlocks = 255;
+
+// Device-time phases of the KKT core (timing mode), with the algorithmic
+// work of one occurrence (one factorisation / one substitution sweep).
+// kPhTail: the look-ahead dense-tail factor (k_tail_pr and its repair launches).
+enum KktPhase { kPhGather = 0, kPhDiag, kPhTrsm, kPhSyrk, kPhForward, kPhBackward, kPhTail, kNumPhases };
+
+// Item pairs and triples, laid out as HIP's int2 / int3 / uint2 (asserted
+// where they are uploaded as such)
+struct SchedInt2 { int x, y; };
+struct SchedInt3 { int x, y, z; };
+struct SchedUint2 { unsigned x, y; };
+
+// The paths that the knobs and the plan select together
+struct KktPaths {
+    bool visits = false;       // the deep-tree gather schedule and the sweeps' pre-pass
+    bool chain_lead = false;   // forward dense-tail sweep by one lead workgroup + helpers (k_tail_fwd_lead)
+    bool tail_run = false;     // the dense tail as one persistent launch (k_tail_run)
+    bool run_winpub = false;   // the run's window hand-off (TailRun::pub)
+    int small_leaves = 0;      // knobs.small_leaves, unset: kSmallLeafMinCount
+    int sf_width = 0;          // widest level of the sync-free range (build_sync_free_plan)
+};
+KktPaths kkt_paths(const KktPlan& P, const KktKnobs& knobs);
+
+// What the launch code reads on the host: per-level and per-group pointers
+// and counts, strides and flags.  Everything else a step builds is a local of
+// that step, gone once uploaded.
+struct KktLaunch {
+    KktPaths paths;
+    // panels
+    std::vector<int> fu_ptr;         // per level: fused panel units [fu_ptr[l], fu_ptr[l+1])
+    std::vector<int> small_ptr;      // per level: small panels [small_ptr[l], small_ptr[l+1]) (k_panel_s)
+    std::vector<char> split_level;   // per level: k_diag + k_trsm instead of the fused panels (wide levels)
+    std::vector<int> small1_cnt;     // per level: leading single-column small panels of <= 8 rows (k_panel_s1)
+    // sweeps
+    std::vector<int> chunk_ptr;      // per level: solve chunks [chunk_ptr[l], chunk_ptr[l+1])
+    std::vector<int> leaf_cnt;       // per level: leading single-column supernodes of the sweep order
+    std::vector<int> leaf8_cnt;      // per level: the first of them, small leaves (k_fwd_leaf8 / k_bwd_leaf8)
+    size_t partial_stride = 1;       // backward partial sums of one right-hand side
+    int sf_level = 0;                // first level of the sync-free range (nlevels: none)
+    int nsf_f = 0, nsf_b = 0;        // its forward / backward items
+    int pre_cols = 0;                // columns of the deep-tree pre-pass (k_fwd_pre)
+    size_t ybuf_stride = 1, zpad_stride = 1;
+    int fwd_launches = 0, bwd_launches = 0;   // kernel launches per substitution sweep
+    // gather groups (sparse level l, group nlevels = tail)
+    std::vector<int> ck_ptr;         // per group: chunks [ck_ptr[g], ck_ptr[g+1])
+    std::vector<int> ck_kind;        // per group: 0 k_update, 1 k_update_flat, 2 k_update_quad
+    std::vector<char> ck_wide;       // per group: partials summed four at a time (few chunks, units split >= 4 ways)
+    // dense tail
+    std::vector<int> visit_ptr;      // TailView::vptr (empty: the visit_hi formula alone)
+    std::vector<int> run_ptr;        // first item of each launch of the persistent run
+};
+
+// Fused panel units (k_panel_w) and small panels (k_panel_s) per level
+struct PanelUnits {
+    std::vector<int> fu_sup, fu_j;   // fused unit -> supernode, tile pair index
+    std::vector<int> small_sups;
+    std::vector<int> fu_ptr, small_ptr, small1_cnt;
+    std::vector<char> split_level;
+};
+PanelUnits build_panel_units(const KktPlan& P, const KktKnobs& knobs, const KktPaths& paths);
+
+// Solve chunks of the chunked levels
+struct SolveChunks {
+    std::vector<int> chunk_sup, chunk_r0;
+    std::vector<int> sup_chunk0;     // per supernode: first solve chunk (-1: not chunked)
+    std::vector<int> chunk_ptr;
+    size_t partial_stride = 1;
+};
+SolveChunks build_solve_chunks(const KktPlan& P);
+
+// level_sups in sweep order (leaves first on unchunked levels)
+struct SweepOrder {
+    std::vector<int> sweep_sups;
+    std::vector<int> leaf_cnt, leaf8_cnt;
+};
+SweepOrder build_sweep_order(const KktPlan& P, const KktPaths& paths, const SolveChunks& ch);
+
+// Sync-free top levels of the sweeps (k_fwd_sf / k_bwd_sf)
+struct SyncFreePlan {
+    int sf_level = 0;
+    std::vector<int> ybase;          // per supernode (+ end): first ybuf slot of its update values
+    std::vector<int> yrow_idx;       // the plan's, through the moved slices
+    std::vector<int> zbase, zpi, need, par;
+    std::vector<SchedInt2> items_f, items_b;   // (s, -1) whole supernode, (s, c >= 0) solve chunk c
+    size_t ybuf_stride = 1, zpad_stride = 1;
+    // deep trees (paths.visits, a range exists): late lists and the pre-pass
+    bool late_lists = false;
+    std::vector<int> ylate_ptr, ylate_idx, pre_col, pre_ptr, pre_idx;
+    bool range(const KktPlan& P) const { return sf_level < P.nlevels; }
+};
+SyncFreePlan build_sync_free_plan(const KktPlan& P, const KktKnobs& knobs, const KktPaths& paths,
+                                  const SolveChunks& ch);
+
+// Deep trees: the sparse units' k-slots in visit order (empty without visits)
+struct VisitSlots {
+    std::vector<int> kslot, kptr, late_b;        // the slots; per unit: its range's end, its first late slot
+    std::vector<std::vector<SchedInt3>> vis;     // per gather group: (unit, slot begin, slot end)
+};
+VisitSlots build_visit_slots(const KktPlan& P, const KktKnobs& knobs, const KktPaths& paths);
+
+// Split-K gather chunks per group
+struct GatherChunks {
+    std::vector<int> ck_u, ck_b, ck_e, ck_part;
+    std::vector<int> ck_q;           // split-unit index of each chunk (-1: unsplit)
+    std::vector<int> sp_u, sp_p0, sp_n;
+    std::vector<int> ck_ptr, sp_ptr, ck_kind;
+    std::vector<char> ck_wide;
+    size_t split_cnt = 1;            // arrival counters of the split units
+    size_t partial_tiles = 1;        // partial tiles of the largest group
+};
+GatherChunks build_gather_chunks(const KktPlan& P, const KktKnobs& knobs, const KktPaths& paths,
+                                 const VisitSlots& vs);
+
+// Launches per sweep and algorithmic work per phase occurrence
+struct WorkCounts {
+    int fwd_launches = 0, bwd_launches = 0;
+    double flops[kNumPhases] = {}, bytes[kNumPhases] = {};
+};
+WorkCounts count_work(const KktPlan& P, const KktKnobs& knobs, const std::vector<int>& chunk_ptr,
+                      const std::vector<int>& leaf_cnt, const std::vector<int>& leaf8_cnt, int sf_level);
+
+// Per-task source descriptors and per-slot records of the gather
+std::vector<TaskSrc> build_task_src(const KktPlan& P, const std::vector<TailTask>& ts);
+std::vector<SlotRec> build_slot_records(const KktPlan& P, const std::vector<int>& kslot,
+                                        const std::vector<TailTask>& ts);
+
+// ---- the dense tail's host schedules
+
+// Visits of launch t: block column c receives the updates of blocks 0 .. c - 2
+// in chunks of K = TailView::vk, the latest chunk in launch c - 1, the one
+// before in launch c - 2, ...: launch c - 1 - k applies blocks
+// [c - 1 - K (k + 1), c - 1 - K k) (clipped at 0) -- every block available
+// (b < t) and every column done before its panel, block c - 1 being the
+// panel's own pre-update.  visit_hi: the end of the chunk launch t applies to
+// column c (<= 0: none).
+constexpr inline int visit_hi(int t, int c, int K) { return c - 1 - K * (c - 1 - t); }
+
+// visit tiles of launch t (tail of ntb block columns, chunks of K blocks)
+int tail_visit_tiles(int ntb, int t, int K);
+// The visits of every look-ahead launch placed so that no launch needs more
+// than `cap` workgroups (one round on `cap` CUs): visit_hi's chunks, with
+// tiles' first chunks moved into earlier launches where a launch would
+// overflow.  xcd: a column's visits grouped on one XCD within each launch.
+// Returns the list (TailView::vlist layout) and ptr[0..ntb].
+std::vector<unsigned> tail_visit_schedule(int ntb, int nt, int K, int cap, bool xcd, std::vector<int>& ptr);
+// Items per launch t (ptr[t] .. ptr[t + 1]): panel workgroups (j, t | chunks
+// of column t << 8 | 1 << 31), then visits (bi | c << 8 | b0 << 16 | b1 << 24,
+// t | chunk index << 8), column t + 1's first.  Column c's chunks: the latest
+// L blocks before c - 1 in launch c - 1, then K at a time in launches c - 2,
+// ...; launches over `cap` items move first chunks earlier.
+std::vector<SchedUint2> tail_run_schedule(int ntb, int nt, int K, int L, int cap, std::vector<int>& ptr);
+// algorithmic flops / bytes of every visit of one factorisation
+void tail_visit_work(int ntb, int nt, int K, double& flops, double& bytes);
+
+// The schedules of the plan's dense tail (empty where a path is off)
+struct TailSchedule {
+    std::vector<unsigned> visit_list;     // TailView::vlist
+    std::vector<int> visit_ptr;
+    std::vector<SchedUint2> run_items;
+    std::vector<int> run_ptr;
+};
+TailSchedule build_tail_schedule(const KktPlan& P, const KktKnobs& knobs, const KktPaths& paths, int cus);
+
+// Every part, in the KktDevice constructor's order (tests and tools; the
+// constructor calls the parts itself and drops each after its upload)
+struct KktSchedule {
+    KktPaths paths;
+    PanelUnits panels;
+    SolveChunks chunks;
+    SweepOrder order;
+    SyncFreePlan sf;
+    VisitSlots visits;
+    GatherChunks gather;
+    WorkCounts work;
+    std::vector<TaskSrc> usrc, tsrc;
+    std::vector<SlotRec> slot_rec, tail_slot_rec;
+    TailSchedule tail;
+};
+KktSchedule build_kkt_schedule(const KktPlan& P, const KktKnobs& knobs, int cus);
+
+}  // namespace ipo

@@ -80,7 +80,7 @@ EXPORTED = [
     "ipo_hip_set_device", "ipo_hip_rccl_unique_id", "ipo_hip_ctx_create_shard", "ipo_hip_vector_bench",
     "ipo_hip_dot_ordered",
     "ipo_hip_kkt_create_q", "ipo_hip_ldlt_set_q", "ipo_hip_symbolic_q", "ipo_hip_mps_quads",
-    "ipo_hip_symbolic_tail",
+    "ipo_hip_symbolic_tail", "ipo_hip_kkt_schedule",
     "ipo_hip_solve_qp", "ipo_hip_ctx_create_qp", "ipo_hip_mps_load_qp",
 ]
 
@@ -185,6 +185,8 @@ def lib() -> C.CDLL:
     L.ipo_hip_symbolic_forced.restype = _I
     L.ipo_hip_symbolic_tail.argtypes = [_I, _I, _P, _P, _D, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]
     L.ipo_hip_symbolic_tail.restype = _I
+    L.ipo_hip_kkt_schedule.argtypes = [_I, _I, _P, _P, _I, _I, C.c_char_p, _P, C.c_long]
+    L.ipo_hip_kkt_schedule.restype = C.c_long
     L.ipo_hip_set_device.argtypes = [_I]
     L.ipo_hip_set_device.restype = _I
     L.ipo_hip_rccl_unique_id.argtypes = [_P]
@@ -654,6 +656,36 @@ def symbolic_tail(m, n, kA, iA, density=None) -> dict:
     if rc:
         raise IpoHipError("symbolic_tail: " + last_error())
     return dict(tail_c0=tc.value, nt=nt.value, ntb=ntb.value)
+
+
+def kkt_schedule(m, n, kA, iA, names, cus=256, nforced=0):
+    """Host-only: integer arrays (by name, see ipo_hip.h) of the launch
+    schedule a KktFactor of this pattern builds on a device of `cus` compute
+    units, at the knobs of the environment; pairs and triples flattened.
+    names: one name (returns its array) or a list (returns a dict, read from
+    one build of the plan)."""
+    kA = np.ascontiguousarray(kA, np.int32)
+    iA = np.ascontiguousarray(iA, np.int32)
+    many = not isinstance(names, str)
+    arg = (",".join(names) if many else names).encode()
+    f = lib().ipo_hip_kkt_schedule
+    out = np.zeros(1 << 22, np.int32)
+    n_out = f(m, n, _ptr(kA), _ptr(iA), nforced, cus, arg, _ptr(out), out.size)
+    if n_out > out.size:
+        out = np.zeros(n_out, np.int32)
+        n_out = f(m, n, _ptr(kA), _ptr(iA), nforced, cus, arg, _ptr(out), out.size)
+    if n_out < 0:
+        raise IpoHipError(last_error())
+    if not many:
+        return out[:n_out].copy()
+    d, pos = {}, 0
+    for nm in names:
+        k = int(out[pos])
+        d[nm] = out[pos + 1:pos + 1 + k].copy()
+        pos += 1 + k
+    if pos != n_out:
+        raise IpoHipError("kkt_schedule: the arrays do not add up to the returned length")
+    return d
 
 
 # ----------------------------------------------------------------- synthetic LPs

@@ -5,7 +5,8 @@
 // against a host LDL' (nt <= 2048) and, built with -DIPO_PANEL_STAMPS, the
 // in-kernel clock stamps of workgroup 0 of one step are printed.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off [-DIPO_PANEL_STAMPS] \
-//         -I linear-programming-vanderbei_amd/csrc tools/ubench_tail.hip -o tools/ubench_tail
+//         -I linear-programming-vanderbei_amd/csrc tools/ubench_tail.hip \
+//         linear-programming-vanderbei_amd/csrc/kkt_schedule.cpp -o tools/ubench_tail
 //   tools/ubench_tail [nt] [reps] [stamp step]
 #include "../linear-programming-vanderbei_amd/csrc/kkt_dense.hip"
 
@@ -76,7 +77,7 @@ int main(int argc, char** argv) {
         CK(hipDeviceGetAttribute(&cus_run, hipDeviceAttributeMultiprocessorCount, 0));
         if (const char* cp = std::getenv("UB_CAP")) cus_run = std::atoi(cp);   // the schedule's items per launch
         const int latest = std::getenv("UB_LATEST") ? std::atoi(std::getenv("UB_LATEST")) : ipo::kTailVisitLatest;
-        const std::vector<uint2> items = ipo::tail_run_schedule(ntb, nt, tv.vk, latest, cus_run, rptr);
+        const std::vector<ipo::SchedUint2> items = ipo::tail_run_schedule(ntb, nt, tv.vk, latest, cus_run, rptr);
         CK(hipMalloc(&ditems, items.size() * sizeof(uint2)));
         CK(hipMemcpy(ditems, items.data(), items.size() * sizeof(uint2), hipMemcpyHostToDevice));
         CK(hipMalloc(&dcnt, ncnt * sizeof(int)));
