@@ -15,10 +15,6 @@ namespace ipo {
 
 namespace {
 
-constexpr int TR = kTileRows;     // 64
-constexpr int PC = kPanelCols;    // 64
-constexpr int NT = 256;
-
 // What the diagonal-block routines need from the plan, passed by value: a
 // reference to the kernel's PlanView argument would force a copy of it into
 // scratch memory (and a scratch load per use) once a non-inlined callee
@@ -1590,11 +1586,6 @@ k_tail_pr(PlanView p, TailView tv, int t, int gp, int vbase) {
 // is skipped without counting, and the host repair resumes the run from
 // step tb + 1 with the counters as they are.
 __host__ __device__ __forceinline__ int tail_gp(int nt, int t) { return max(1, (nt - t * PC + TR - 1) / TR - 1); }
-// visits (chunks) of block column c in the persistent schedules (run_chunks)
-__host__ __device__ __forceinline__ int run_chunk_count(int c, int K, int L) {
-    return c <= 1 ? 0 : 1 + (max(0, c - 1 - L) + K - 1) / K;
-}
-
 
 __global__ void __launch_bounds__(PNT)
 k_tail_run(PlanView p, TailView tv, TailRun rc) {

@@ -190,6 +190,10 @@ class KktDevice {
     void build_slot_records(const std::vector<int>& kslot_v);
     void setup_tail(int cus);
     void alloc_numeric();
+    // (kkt_sweep.hip) the dynamic-LDS limit of the sweep kernels this plan
+    // launches: the sync-free ones, or the dense tail's chain, pair and lead kernels
+    void raise_sweep_lds(bool sync_free);
+    void dump_sf_stamps() const;   // (kkt_sweep.hip) ~KktDevice's developer dump; nothing without -DIPO_SF_STAMPS
     KktLaunch h_;                  // what the launch code reads of the schedule on the host
     PlanView plan_view() const;
     // the host repair backs the look-ahead panel's dependent pivots (TailView::dep):
@@ -200,7 +204,7 @@ class KktDevice {
     int dump_count_ = 0;
     TailView tail_view() const;
     template <int R>
-    void sweep(double* dz, const double* epsp);
+    void sweep(double* dz, const double* epsp);   // rawsolve's sweeps, sf_tbase, tail_rhs_*: kkt_sweep.hip
     void sweep_blocked(double* dz, const double* epsp);
     void tail_rhs_begin(double* dz, int R);
     void tail_rhs_end(double* dz, int R);

@@ -1,5 +1,6 @@
-// kkt_kernels.h -- what the KKT kernel translation units share: the device
-// view of the symbolic plan and the launchers of the dense per-panel kernels
+// kkt_kernels.h -- what the KKT kernel translation units share: the tile
+// constants, the device view of the symbolic plan, the hand-off accesses
+// and the launchers of the dense per-panel kernels
 // (kkt_dense.hip), which live in their own translation unit because their
 // fully unrolled register code dominates compile time.  (The dense tail's
 // host schedules: kkt_schedule.h.)
@@ -13,6 +14,10 @@
 #include "kkt_plan.h"
 
 namespace ipo {
+
+constexpr int TR = kTileRows;     // 64
+constexpr int PC = kPanelCols;    // 64
+constexpr int NT = 256;           // threads per workgroup
 
 struct PlanView {
     const int* col0;
