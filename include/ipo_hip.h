@@ -121,8 +121,11 @@ double ipo_hip_ctx_setup_seconds(const ipo_hip_ctx *ctx);
  * ascending in each column: the layout of ipo_hip_ldlt_set_q), checked; it
  * must be positive semidefinite, which is NOT checked: a non-convex Q gives
  * an unspecified status.  kQ == NULL: an empty Q (the LP, by the QP loop).
- * One thread walks one column of Q serially: meant for sparse Q (a Q with
- * columns of thousands of entries runs, slowly).  Returns as ipo_hip_solve;
+ * Q x is formed column by column: a column of fewer than IPO_HIP_Q_LONG
+ * entries (default 256) by one thread in row order, a longer one (a dense
+ * covariance or Gram matrix, the dense rows and columns of an arrow Q) by
+ * one wave in a fixed order of its own (ipo_hip_q_times states it), so the
+ * threshold moves results by rounding only.  Returns as ipo_hip_solve;
  * an invalid Q returns 7 (ipo_hip_last_error).  No sharding, no HSD for QPs. */
 int ipo_hip_solve_qp(int m, int n, int nz, const int *iA, const int *kA, const double *A, const double *b,
                      const double *c, double f, const int *kQ, const int *iQ, const double *Q, double *x,
@@ -279,6 +282,24 @@ int ipo_hip_vector_bench(int m, int n, const int *kA, const int *iA, const doubl
  * k_reduce_ordered).  Test entry (no reference counterpart: dotprod is
  * internal to the reference).  Returns 0, or -1 (ipo_hip_last_error). */
 int ipo_hip_dot_ordered(const double *a, const double *b, int n, double *out);
+
+/* out[j] = sum_k Q[k] v[iQ[k]] over column j of Q (n x n CSC, k in [kQ[j],
+ * kQ[j + 1])) on host vectors, by the rule the QP solver and the KKT
+ * refinement form Q x with.  A column of fewer than long_min entries: one
+ * running sum in k order.  A column of at least long_min entries: 64 running
+ * sums, sum l from +0 over the entries kb + l, kb + l + 64, ... in k order,
+ * then s[l] += s[l + o] for o = 32, 16, 8, 4, 2, 1; the result is s[0].
+ * Products are rounded before they are added.  long_min <= 0: the value of
+ * IPO_HIP_Q_LONG (default 256; 0: no column is long).  An empty column is
+ * never long.  kQ must start at 0 and not decrease and iQ must lie in
+ * [0, n); Q is NOT required to be symmetric, nor its rows to be sorted.
+ * Test entry (no reference counterpart).  Returns 0, or -1
+ * (ipo_hip_last_error). */
+int ipo_hip_q_times(int n, const int *kQ, const int *iQ, const double *Q, const double *v, int long_min,
+                    double *out);
+/* How many columns of Q the object sums by one wave each (0 without Q). */
+int ipo_hip_kkt_q_long(const ipo_hip_kkt *k);
+int ipo_hip_ctx_q_long(const ipo_hip_ctx *ctx);
 
 int ipo_hip_synth_random(int m, int n, int per_col, int band, unsigned long long seed, int *nz, int *kA, int *iA,
                          double *A, double *b, double *c, double *xs, double *ys, double *ws, double *zs);

@@ -202,6 +202,7 @@ struct ipo_hip_kkt {
 
 namespace ipo {
 double dot_ordered_host(const double* a, const double* b, int n);   // dev_common.hip
+void q_times_host(int n, const int* kQ, const int* iQ, const double* Q, const double* v, int thr, double* out);
 }
 
 extern "C" {
@@ -958,6 +959,29 @@ int ipo_hip_dot_ordered(const double* a, const double* b, int n, double* out) {
         return -1;
     }
 }
+
+int ipo_hip_q_times(int n, const int* kQ, const int* iQ, const double* Q, const double* v, int long_min,
+                    double* out) {
+    try {
+        if (n < 0 || !kQ || !out || (n > 0 && !v)) throw std::invalid_argument("q_times: bad arguments");
+        if (kQ[0] != 0) throw std::invalid_argument("q_times: kQ[0] != 0");
+        for (int j = 0; j < n; j++)
+            if (kQ[j + 1] < kQ[j]) throw std::invalid_argument("q_times: kQ decreasing at column " + std::to_string(j));
+        if (n > 0 && kQ[n] > 0 && (!iQ || !Q)) throw std::invalid_argument("q_times: bad arguments");
+        for (int k = 0; k < (n > 0 ? kQ[n] : 0); k++)
+            if (iQ[k] < 0 || iQ[k] >= n) throw std::invalid_argument("q_times: row index out of range at entry " + std::to_string(k));
+        const int thr = long_min > 0 ? long_min : ipo::KktKnobs::from_env().q_long;
+        ipo::q_times_host(n, kQ, iQ, Q, v, thr, out);
+        return 0;
+    } catch (const std::exception& e) {
+        set_err(e.what());
+        return -1;
+    }
+}
+
+int ipo_hip_kkt_q_long(const ipo_hip_kkt* k) { return k->kkt->q_long_count(); }
+
+int ipo_hip_ctx_q_long(const ipo_hip_ctx* ctx) { return ctx->solver->kkt().q_long_count(); }
 
 int ipo_hip_synth_random(int m, int n, int per_col, int band, unsigned long long seed, int* nz, int* kA, int* iA,
                          double* A, double* b, double* c, double* xs, double* ys, double* ws, double* zs) {

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "row_ax.h"
 
 namespace ipo {
@@ -192,5 +194,26 @@ double dot_ordered_host(const double* a, const double* b, int n);
 // sum_k At[k] x[iAt[k]] for rows mrow <= i < m (CSR of A), one wave per row.
 void launch_link_ax(int mrow, int m, const int* kAt, const int* iAt, const double* At, const double* x, double* out,
                     hipStream_t st);
+
+// Long columns of Q (CSC; symmetric, so column j is row j of Q v): for each
+// listed column j = cols[s], s < nl, one wave forms out[j] = sum_k Q[k]
+// v[iQ[k]] over k in [kQ[j], kQ[j + 1]) in launch_link_ax's order: lane l
+// sums its entries kb + l, kb + l + 64, ... in increasing k from +0, the 64
+// lane sums are combined by wave_sum -- a fixed order, not sparse_dot's.
+// out is a full-length vector; entries of unlisted columns are not written.
+// cols (device) may list any columns, in any order, once each.
+void launch_q_long(int nl, const int* cols, const int* kQ, const int* iQ, const double* Q, const double* v,
+                   double* out, hipStream_t st);
+// whether column j is one of them at threshold thr (KktKnobs::q_long; 0:
+// never): the rule of the host list (q_long_columns) and of the kernels that
+// read launch_q_long's value instead of calling sparse_dot
+__host__ __device__ inline bool q_col_long(const int* kQ, int j, int thr) {
+    return thr > 0 && kQ[j + 1] - kQ[j] >= thr;
+}
+std::vector<int> q_long_columns(int n, const int* kQ, int thr);   // host kQ; ascending
+// Q v of host arrays (Q n x n CSC, not necessarily symmetric) by that rule:
+// long columns through launch_q_long, the others through sparse_dot (tests:
+// ipo_hip_q_times)
+void q_times_host(int n, const int* kQ, const int* iQ, const double* Q, const double* v, int thr, double* out);
 
 }  // namespace ipo

@@ -261,6 +261,105 @@ void launch_link_ax(int mrow, int m, const int* kAt, const int* iAt, const doubl
     IPO_HIP_CHECK(hipGetLastError());
 }
 
+// Long columns of Q (dev_common.h launch_q_long): k_link_ax's order -- lane
+// l one running sum from +0 over its entries kb + l, kb + l + 64, ... in
+// increasing k (products rounded before they are added), the 64 lane sums by
+// wave_sum -- with kQLongSteps steps of a lane's index and value loads in
+// flight and their x loads issued together, as sparse_dot does (one dependent
+// load pair per step left a column of thousands of entries latency-bound).
+// Consecutive lanes read consecutive k.  The last, partly filled batch loads
+// a clamped entry in the lanes past the end (no branch around a load) and
+// leaves their sums as they are.
+constexpr int kQLongSteps = 4;
+
+__global__ void __launch_bounds__(256)
+k_q_long(int nl, const int* __restrict__ cols, const int* __restrict__ kQ, const int* __restrict__ iQ,
+         const double* __restrict__ Q, const double* __restrict__ v, double* __restrict__ out) {
+    const int sl = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (sl >= nl) return;
+    const int j = cols[sl];
+    const int ke = kQ[j + 1];
+    int k0 = kQ[j];
+    double s = 0.0;
+    for (; ke - k0 >= kQLongSteps * 64; k0 += kQLongSteps * 64) {
+        int ix[kQLongSteps];
+        double a[kQLongSteps], b[kQLongSteps];
+#pragma unroll
+        for (int u = 0; u < kQLongSteps; u++) { ix[u] = iQ[k0 + u * 64 + lane]; a[u] = Q[k0 + u * 64 + lane]; }
+#pragma unroll
+        for (int u = 0; u < kQLongSteps; u++) b[u] = v[ix[u]];
+#pragma unroll
+        for (int u = 0; u < kQLongSteps; u++) s += a[u] * b[u];
+    }
+    if (k0 < ke) {
+        int ix[kQLongSteps];
+        double a[kQLongSteps], b[kQLongSteps];
+#pragma unroll
+        for (int u = 0; u < kQLongSteps; u++) {
+            const int k = min(k0 + u * 64 + lane, ke - 1);
+            ix[u] = iQ[k];
+            a[u] = Q[k];
+        }
+#pragma unroll
+        for (int u = 0; u < kQLongSteps; u++) b[u] = v[ix[u]];
+#pragma unroll
+        for (int u = 0; u < kQLongSteps; u++) {
+            const double t = s + a[u] * b[u];
+            s = k0 + u * 64 + lane < ke ? t : s;
+        }
+    }
+    s = wave_sum(s);
+    if (lane == 0) out[j] = s;
+}
+
+void launch_q_long(int nl, const int* cols, const int* kQ, const int* iQ, const double* Q, const double* v,
+                   double* out, hipStream_t st) {
+    if (nl <= 0) return;
+    hipLaunchKernelGGL(k_q_long, dim3((nl + 3) / 4), dim3(256), 0, st, nl, cols, kQ, iQ, Q, v, out);
+    IPO_HIP_CHECK(hipGetLastError());
+}
+
+std::vector<int> q_long_columns(int n, const int* kQ, int thr) {
+    std::vector<int> cols;
+    if (thr > 0)
+        for (int j = 0; j < n; j++)
+            if (kQ[j + 1] - kQ[j] >= thr) cols.push_back(j);
+    return cols;
+}
+
+// the columns launch_q_long does not take: one thread each, sparse_dot's order
+__global__ void __launch_bounds__(256)
+k_q_short(int n, int thr, const int* __restrict__ kQ, const int* __restrict__ iQ, const double* __restrict__ Q,
+          const double* __restrict__ v, double* __restrict__ out) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n || q_col_long(kQ, j, thr)) return;
+    out[j] = sparse_dot(kQ[j], kQ[j + 1], Q, iQ, v);
+}
+
+// Test entry (ipo_hip_q_times): Q v of host arrays by the solver's rule, on
+// the default stream.
+void q_times_host(int n, const int* kQ, const int* iQ, const double* Q, const double* v, int thr, double* out) {
+    if (n <= 0) return;
+    const int nz = kQ[n];
+    DevBuf<int> dk(n + 1), di(std::max(1, nz)), dcols;
+    DevBuf<double> dq(std::max(1, nz)), dv(n), dout(n);
+    IPO_HIP_CHECK(hipMemcpy(dk.get(), kQ, (n + 1) * sizeof(int), hipMemcpyHostToDevice));
+    IPO_HIP_CHECK(hipMemcpy(di.get(), iQ, nz * sizeof(int), hipMemcpyHostToDevice));
+    IPO_HIP_CHECK(hipMemcpy(dq.get(), Q, nz * sizeof(double), hipMemcpyHostToDevice));
+    IPO_HIP_CHECK(hipMemcpy(dv.get(), v, n * sizeof(double), hipMemcpyHostToDevice));
+    const std::vector<int> cols = q_long_columns(n, kQ, thr);
+    const int nl = static_cast<int>(cols.size());
+    if (nl > 0) {
+        dcols.alloc(nl);
+        IPO_HIP_CHECK(hipMemcpy(dcols.get(), cols.data(), nl * sizeof(int), hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(k_q_short, dim3((n + 255) / 256), dim3(256), 0, nullptr, n, thr, dk.get(), di.get(), dq.get(),
+                       dv.get(), dout.get());
+    IPO_HIP_CHECK(hipGetLastError());
+    launch_q_long(nl, dcols.get(), dk.get(), di.get(), dq.get(), dv.get(), dout.get(), nullptr);
+    IPO_HIP_CHECK(hipMemcpy(out, dout.get(), n * sizeof(double), hipMemcpyDeviceToHost));
+}
+
 // Column-sliced row products (A x, row i summed over its columns in
 // ascending order like sparse_dot): pass p adds the entries of the columns
 // of slice p to the carried sum, so each pass gathers from one slice of x

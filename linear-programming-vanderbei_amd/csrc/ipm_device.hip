@@ -300,7 +300,10 @@ k_pf_directions(int m, int n, double mu, const double* __restrict__ x, const dou
 // k_pf_residuals with the quadratic term: for column j, (Q x)_j over Q's
 // column j (= its row j: Q is symmetric) in row order, kept in qx for the
 // objectives' x'Qx and subtracted last, sigma = ((c - A'y) + z) - Q x.  One
-// thread walks one column of Q serially (sparse Q).  Not sharded: no mcnt.
+// thread walks a column of Q serially (sparse_dot), but a column of at least
+// qthr > 0 entries (KktDevice::q_long_min) is read from qx, where
+// KktDevice::launch_q_long has summed it by one wave beforehand (dense and
+// arrow Q).  Not sharded: no mcnt.
 __global__ void __launch_bounds__(kResThreads)
 k_qp_residuals(int m, int n, const int* __restrict__ kAt, const int* __restrict__ iAt, const double* __restrict__ At,
                const int* __restrict__ kA, const int* __restrict__ iA, const double* __restrict__ A,
@@ -308,7 +311,7 @@ k_qp_residuals(int m, int n, const int* __restrict__ kAt, const int* __restrict_
                const double* __restrict__ b, const double* __restrict__ c, const double* __restrict__ x,
                const double* __restrict__ y, const double* __restrict__ w, const double* __restrict__ z,
                double* __restrict__ rho, double* __restrict__ sig, double* __restrict__ qx, double* __restrict__ part,
-               int mrow, const double* __restrict__ lax) {
+               int mrow, const double* __restrict__ lax, int qthr) {
     __shared__ double sh[kResThreads / 64];
     double sr = 0.0, ss = 0.0;
     for (int i = blockIdx.x * kResThreads + threadIdx.x; i < m + n; i += kRedBlocks * kResThreads) {
@@ -323,7 +326,7 @@ k_qp_residuals(int m, int n, const int* __restrict__ kAt, const int* __restrict_
         } else {
             const int j = i - m;
             const double aty = sparse_dot(kA[j], kA[j + 1], A, iA, y);
-            const double q = sparse_dot(kQ[j], kQ[j + 1], Q, iQ, x);
+            const double q = q_col_long(kQ, j, qthr) ? qx[j] : sparse_dot(kQ[j], kQ[j + 1], Q, iQ, x);
             const double s = ((c[j] - aty) + z[j]) - q;
             qx[j] = q;
             sig[j] = s;
@@ -902,9 +905,10 @@ int IpmSolver::run_qp(const IpmOptions& opt, IpmResult* res) {
     int status = 5, iter;
     for (iter = 0; iter < opt.max_iter; iter++) {
         row_ax(x_.get(), s);
+        if (K.q_long_count() > 0) K.launch_q_long(x_.get(), qx_.get());     // Q's long columns, one wave each
         hipLaunchKernelGGL(k_qp_residuals, dim3(kRedBlocks), dim3(kResThreads), 0, s, m, n, K.kA(), K.iA(), K.A(), K.kAt(),
                            K.iAt(), K.At(), K.kQ(), K.iQ(), K.Q(), b_.get(), c_.get(), x_.get(), y_.get(), w_.get(), z_.get(), rho_.get(),
-                           sig_.get(), qx_.get(), part_.get(), mrow(), lax());
+                           sig_.get(), qx_.get(), part_.get(), mrow(), lax(), K.q_long_min());
         hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 2, 0u, scal_.get() + 8);
         RedJobs j{};
         j.nj = 5;

@@ -127,6 +127,16 @@ class KktDevice {
     const int* kQ() const { return qnz_ > 0 ? dkQ_.get() : nullptr; }
     const int* iQ() const { return qnz_ > 0 ? diQ_.get() : nullptr; }
     const double* Q() const { return qnz_ > 0 ? dQ_.get() : nullptr; }
+    // The columns of Q with at least knobs_.q_long entries (IPO_HIP_Q_LONG,
+    // kkt_knobs.h; any columns, not only trailing ones): their products are
+    // summed by one wave each (launch_q_long, dev_common.h) instead of one
+    // thread's serial sparse_dot, in the refinement's residual and in
+    // IpmSolver::run_qp's.  0 without Q.
+    int q_long_count() const { return q_long_n_; }
+    int q_long_min() const { return q_long_n_ > 0 ? knobs_.q_long : 0; }   // the kernels' threshold (0: none)
+    // out[j] = (Q v)_j for those columns, on the object's stream; the other
+    // entries of out (m values) are not written
+    void launch_q_long(const double* v, double* out);
 
     // Numeric factorisation of K(E, D); E (m), D (n) are device vectors.
     void factor(const double* dE, const double* dD);
@@ -258,6 +268,9 @@ class KktDevice {
     DevBuf<int> dkQ_, diQ_;
     DevBuf<double> dQ_, dQdiag_;
     DevBuf<int64_t> dqmap_;
+    int q_long_n_ = 0;             // columns of Q summed by one wave each (q_long_count)
+    DevBuf<int> dQLongCols_;       // [q_long_n_] those columns, ascending
+    DevBuf<double> dLongQ_;        // [2 * m] their products Q dy per right-hand side (full-length vectors)
     // plan
     DevBuf<int> dcol0_, drowptr_, drows_, dperm_, diperm_;
     DevBuf<int64_t> doff_, damap_, ddslot_, drelptr_;

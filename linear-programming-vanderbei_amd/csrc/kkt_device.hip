@@ -795,7 +795,8 @@ __device__ __forceinline__ void kkt_residual_body(
     const double* __restrict__ D, const double* __restrict__ fy, const double* __restrict__ fx,
     const double* __restrict__ dy, const double* __restrict__ dx, double* __restrict__ ry, double* __restrict__ rx,
     double* __restrict__ part, int mrow, const double* __restrict__ axl, const int* __restrict__ kQ,
-    const int* __restrict__ iQ, const double* __restrict__ Q, double qmax) {
+    const int* __restrict__ iQ, const double* __restrict__ Q, double qmax, int qthr,
+    const double* __restrict__ qxl) {
     __shared__ double sh[kResThreads / 64];
     double mx = 0.0;
     for (int i = blockIdx.x * kResThreads + threadIdx.x; i < m + n; i += kRedBlocks * kResThreads) {
@@ -805,8 +806,11 @@ __device__ __forceinline__ void kkt_residual_body(
             else
                 s = sparse_dot(kAt[i], kAt[i + 1], At, iAt, dx);
             // a Q block: fy - ((A dx - E dy) - max Q dy), ldlt.c:391-394
-            // (Q symmetric: row i of Q dy summed over its column i in order)
-            const double r = kQ ? fy[i] - ((s - E[i] * dy[i]) - qmax * sparse_dot(kQ[i], kQ[i + 1], Q, iQ, dy))
+            // (Q symmetric: row i of Q dy summed over its column i in order;
+            // a column of at least qthr entries by one wave beforehand, qxl)
+            const double r = kQ ? fy[i] - ((s - E[i] * dy[i]) -
+                                           qmax * (q_col_long(kQ, i, qthr) ? qxl[i]
+                                                                           : sparse_dot(kQ[i], kQ[i + 1], Q, iQ, dy)))
                                 : fy[i] - (s - E[i] * dy[i]);
             ry[i] = r;
             mx = fmax(mx, ref_abs(r));
@@ -832,6 +836,7 @@ struct ResJobs {
     double* ry[2];
     double* rx[2];
     const double* axl[2];
+    const double* qxl[2];     // Q dy of the long columns of Q (launch_q_long), full length; null: none
 };
 // the active systems' residuals, one launch: system q = blockIdx.y writes
 // the partials of slot q (part + q kRedBlocks)
@@ -840,10 +845,10 @@ k_kkt_residual2(int m, int n, const int* __restrict__ kAt, const int* __restrict
                 const int* __restrict__ kA, const int* __restrict__ iA, const double* __restrict__ A,
                 const double* __restrict__ E, const double* __restrict__ D, ResJobs J, double* __restrict__ part,
                 int mrow, const int* __restrict__ kQ, const int* __restrict__ iQ, const double* __restrict__ Q,
-                double qmax) {
+                double qmax, int qthr) {
     const int q = blockIdx.y;
     kkt_residual_body(m, n, kAt, iAt, At, kA, iA, A, E, D, J.fy[q], J.fx[q], J.dy[q], J.dx[q], J.ry[q], J.rx[q],
-                      part + (size_t)q * kRedBlocks, mrow, J.axl[q], kQ, iQ, Q, qmax);
+                      part + (size_t)q * kRedBlocks, mrow, J.axl[q], kQ, iQ, Q, qmax, qthr, J.qxl[q]);
 }
 
 // -min|d| partials, so that the max-finisher yields -min|d| (negated on host)
@@ -965,6 +970,13 @@ void KktDevice::upload_plan(const int* kA, const int* iA, const double* A, const
             for (int k = qb->kQ[j]; k < qb->kQ[j + 1]; k++)
                 if (qb->iQ[k] == j) qd[j] = qb->Q[k];
         dQdiag_.upload(qd, s);
+        // the long columns (kkt_device.h q_long_count), maybe none
+        const std::vector<int> ql = q_long_columns(m, qb->kQ, knobs_.q_long);
+        q_long_n_ = static_cast<int>(ql.size());
+        if (q_long_n_ > 0) {
+            dQLongCols_.upload(ql, s);
+            dLongQ_.alloc(2 * static_cast<size_t>(m));
+        }
         IPO_HIP_CHECK(hipStreamSynchronize(s));
     }
     ddslot_.upload(plan_.dslot, s);
@@ -1667,6 +1679,10 @@ void KktDevice::ph_collect() {
     kev_used_ = 0;
 }
 
+void KktDevice::launch_q_long(const double* v, double* out) {
+    ipo::launch_q_long(q_long_n_, dQLongCols_.get(), dkQ_.get(), diQ_.get(), dQ_.get(), v, out, stream_);
+}
+
 void KktDevice::set_long_rows(int row0) {
     if (xch_ || row0 < 0 || row0 >= m_) return;
     long_row0_ = row0;
@@ -1738,6 +1754,7 @@ void KktDevice::solve_multi(int R, const double* dE, const double* dD, double* c
                 J.ry[nq] = ryv(r); J.rx[nq] = rxv(r);
                 J.axl[nq] = xch_ ? dLinkAx_.get() + (size_t)r * nforced_
                                  : long_row0_ >= 0 ? dLongAx_.get() + (size_t)r * (m - long_row0_) : nullptr;
+                J.qxl[nq] = q_long_n_ > 0 ? dLongQ_.get() + (size_t)r * m : nullptr;
                 nq++;
             }
             hipLaunchKernelGGL(k_perm_out2, dim3(ceil_div(T, NT), nq), dim3(NT), 0, s, T, m, diperm_.get(), P);
@@ -1749,11 +1766,12 @@ void KktDevice::solve_multi(int R, const double* dE, const double* dD, double* c
                 } else if (long_row0_ >= 0) {
                     launch_link_ax(mrow, m, dkAt_.get(), diAt_.get(), dAt_.get(), J.dx[q], axl, s);
                 }
+                if (q_long_n_ > 0) launch_q_long(J.dy[q], const_cast<double*>(J.qxl[q]));
             }
             hipLaunchKernelGGL(k_kkt_residual2, dim3(kRedBlocks, nq), dim3(kResThreads), 0, s, m, n, dkAt_.get(),
                                diAt_.get(), dAt_.get(), dkA_.get(), diA_.get(), dA_.get(), dE, dD, J, dPart_.get(), mrow,
                                dkQ_.get() ? dkQ_.get() : static_cast<const int*>(nullptr), diQ_.get(), dQ_.get(),
-                               static_cast<double>(qmax_));
+                               static_cast<double>(qmax_), q_long_min());
         }
         // residuals and the consistency flags in one read-back
         if (xch_) {

@@ -24,6 +24,9 @@ constexpr int kTailVisitBlocks = 4;
 // finish within one step; equal to the chunk, every tile receives the
 // per-step launches' chunks (bitwise them)
 constexpr int kTailVisitLatest = 4;
+// Entries from which a column of Q is summed by a wave (IPO_HIP_Q_LONG): the
+// long-row threshold of A's linking rows (IpmSolver, kLongRow)
+constexpr int kLongQCol = 256;
 
 struct KktKnobs {
     // ---- switches: the other setting is the same arithmetic in the same
@@ -156,6 +159,14 @@ struct KktKnobs {
     // kOrderedMaxLen entries, else 0; set: max(0, v)): RedJobs::segmin of the
     // solver's dots (dev_common.h)
     int dot_segmin = -1;
+    // IPO_HIP_Q_LONG (unset: kLongQCol = 256; max(0, v); 0 never): columns of
+    // Q with at least this many entries are summed by one wave each
+    // (launch_q_long, dev_common.h: lanes strided, then a wave sum -- a fixed
+    // order, not sparse_dot's) in the QP residual and the refinement's
+    // residual; 0: one thread walks every column serially.  An empty column
+    // is never long.  (The test entry ipo_hip_q_times, capi.cpp, reads it at
+    // each call with long_min <= 0.)  test_gpu_qp_dense.py
+    int q_long = kLongQCol;
 
     // ---- developer diagnostics
 
@@ -235,6 +246,7 @@ struct KktKnobs {
         k.update_xcd = std::max(0, num("IPO_HIP_UPDATE_XCD", 1024));
         k.update_occ = num("IPO_HIP_UPDATE_OCC", 4);
         if (set("IPO_HIP_DOT_SEGMIN")) k.dot_segmin = std::max(0, num("IPO_HIP_DOT_SEGMIN", 0));
+        k.q_long = std::max(0, num("IPO_HIP_Q_LONG", kLongQCol));
         k.setup_times = set("IPO_HIP_SETUP_TIMES");
         k.debug_redo = set("IPO_HIP_DEBUG_REDO");
         k.trace_full = set("IPO_HIP_TRACE_FULL");

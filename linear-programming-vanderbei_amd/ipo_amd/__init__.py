@@ -82,6 +82,7 @@ EXPORTED = [
     "ipo_hip_kkt_create_q", "ipo_hip_ldlt_set_q", "ipo_hip_symbolic_q", "ipo_hip_mps_quads",
     "ipo_hip_symbolic_tail", "ipo_hip_kkt_schedule",
     "ipo_hip_solve_qp", "ipo_hip_ctx_create_qp", "ipo_hip_mps_load_qp",
+    "ipo_hip_q_times", "ipo_hip_kkt_q_long", "ipo_hip_ctx_q_long",
 ]
 
 # int (*)(void *user, double *buf, long n, int op)  -- ipo_hip_allreduce_fn
@@ -174,6 +175,12 @@ def lib() -> C.CDLL:
     L.ipo_hip_ctx_setup_seconds.restype = _D
     L.ipo_hip_dot_ordered.argtypes = [_P, _P, _I, _P]
     L.ipo_hip_dot_ordered.restype = _I
+    L.ipo_hip_q_times.argtypes = [_I, _P, _P, _P, _P, _I, _P]
+    L.ipo_hip_q_times.restype = _I
+    L.ipo_hip_kkt_q_long.argtypes = [_P]
+    L.ipo_hip_kkt_q_long.restype = _I
+    L.ipo_hip_ctx_q_long.argtypes = [_P]
+    L.ipo_hip_ctx_q_long.restype = _I
     L.ipo_hip_vector_bench.argtypes = [_I, _I, _P, _P, _P, _I, _P, _P]
     L.ipo_hip_vector_bench.restype = _I
     L.ipo_hip_synth_random.argtypes = [_I, _I, _I, _I, C.c_ulonglong, C.POINTER(_I)] + [_P] * 9
@@ -468,6 +475,10 @@ class KktFactor:
     def set_epsdiag(self, eps: float):
         lib().ipo_hip_kkt_set_epsdiag(self.h, float(eps))
 
+    def q_long(self) -> int:
+        """Columns of Q summed by one wave each (IPO_HIP_Q_LONG); 0 without Q."""
+        return lib().ipo_hip_kkt_q_long(self.h)
+
     def perm(self) -> np.ndarray:
         p = np.zeros(self.m + self.n, np.int32)
         lib().ipo_hip_kkt_perm(self.h, _ptr(p))
@@ -525,6 +536,10 @@ class Context:
         else:
             status, text = call(None), ""
         return status, st.as_dict(), text
+
+    def q_long(self) -> int:
+        """Columns of Q summed by one wave each (IPO_HIP_Q_LONG); 0 without Q."""
+        return lib().ipo_hip_ctx_q_long(self.h)
 
     def solution(self):
         x = np.zeros(self.p.n); z = np.zeros(self.p.n); y = np.zeros(self.p.m); w = np.zeros(self.p.m)
@@ -732,6 +747,22 @@ def dot_ordered(a, b) -> float:
     if lib().ipo_hip_dot_ordered(_ptr(a), _ptr(b), int(a.size), _ptr(out)):
         raise IpoHipError("dot_ordered: " + last_error())
     return float(out[0])
+
+
+def q_times(q, v, long_min: int = 0) -> np.ndarray:
+    """Q v on the GPU by the solver's rule (ipo_hip_q_times, test entry):
+    q = (kQ, iQ, Q), n x n CSC, not necessarily symmetric; columns of at least
+    long_min entries by one wave each (long_min <= 0: IPO_HIP_Q_LONG's value)."""
+    require_gpu()
+    kQ, iQ, Q = _q_arrays(q)
+    v = np.ascontiguousarray(v, np.float64)
+    n = int(kQ.size) - 1
+    if v.size != n:
+        raise IpoHipError(f"q_times: v has {v.size} entries, Q {n} columns")
+    out = np.zeros(max(n, 1), np.float64)
+    if lib().ipo_hip_q_times(n, _ptr(kQ), _ptr(iQ), _ptr(Q), _ptr(v), int(long_min), _ptr(out)):
+        raise IpoHipError("q_times: " + last_error())
+    return out[:n]
 
 
 def vector_bench(p, reps=20) -> dict:
