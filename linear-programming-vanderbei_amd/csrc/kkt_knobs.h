@@ -56,9 +56,9 @@ struct KktKnobs {
     // lead workgroup + helpers (k_tail_fwd_lead); 0: the per-block chain,
     // bitwise.  test_gpu_panel.py, test_gpu_tail_shapes.py (lead0)
     bool chain_lead = true;
-    // IPO_HIP_CHAIN_PAIRS (default off; on when it parses to non-zero, and
-    // the lead is off): two 64-row blocks per chain workgroup (k_tail_fwd_pair
-    // / k_tail_bwd_pair), bitwise.  test_gpu_panel.py, test_gpu_tail_shapes.py (pairs)
+    // IPO_HIP_CHAIN_PAIRS (default off; on when it parses to non-zero): two
+    // 64-row blocks per workgroup of the backward dense-tail chain
+    // (k_tail_bwd_pair), bitwise.  test_gpu_panel.py, test_gpu_tail_shapes.py (pairs)
     bool chain_pairs = false;
     // IPO_HIP_TAIL_RUN (default on unless it parses to 0; tails of at most
     // kTailSchedMaxBlocks block columns): the look-ahead dense tail as one

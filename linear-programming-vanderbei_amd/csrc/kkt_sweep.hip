@@ -1148,130 +1148,18 @@ k_tail_bwd_chain(PlanView p, TailView tv, SweepVecs V, const double* __restrict_
     }
 }
 
-// The same chains with two 64-row blocks per workgroup ("pairs"): the
+// The backward chain with two 64-row blocks per workgroup ("pairs"): the
 // first block's z is handed to the second inside the workgroup (through LDS
 // after a barrier) instead of through memory, one hand-off per pair instead
 // of per block, while the first block's z is published at once for the
 // workgroups further down the chain.  Every entry sees the arithmetic of
-// k_tail_fwd_chain / k_tail_bwd_chain in the same order (the per-wave
-// partial sums over the earlier blocks, the internal block as their last
-// term, the same wave / column reductions and triangular solves): bitwise
-// the same sweep.  Forward: workgroup g owns blocks a = 2g, b = 2g + 1.
-constexpr size_t kPairFwdLds = 64 * 1024;                                   // dynamic pad: one per CU
+// k_tail_bwd_chain in the same order (the partial sums over the earlier
+// blocks, the internal block as their last term, the same column reductions
+// and triangular solves): bitwise the same sweep.  From the last block:
+// workgroup g owns blocks hi = ntb - 1 - 2g and lo = hi - 1 (none for an
+// odd count's first workgroup).
 constexpr size_t kPairBwdLds = 2 * PC * (PC + 1) * sizeof(double);           // colsum scratch (R <= 2)
 
-template <int R>
-__global__ void __launch_bounds__(NT)
-k_tail_fwd_pair(PlanView p, TailView tv, SweepVecs V, const double* __restrict__ epsp, gran_t* __restrict__ gran,
-                unsigned epoch) {
-    extern __shared__ double lds_pad[];
-    __shared__ double Ls[2][PC][PC + 1];
-    __shared__ int lv[2][PC];
-    __shared__ double zb[R][PC];
-    __shared__ double red[R][4][64];
-    const int nt = tv.nt, tc = tv.tc, ntb = tv.ntb;
-    const int a = 2 * blockIdx.x, b = a + 1;
-    const bool hasb = b < ntb;
-    const int ka = a * PC, nca = min(PC, nt - ka), kb = b * PC, ncb = hasb ? min(PC, nt - kb) : 0;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double eps[R], zown_a[R], zown_b[R];
-    load_eps<R>(epsp, eps);
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        zown_a[r] = (wv == 0 && lane < nca) ? V.z[r * V.zs + tc + ka + lane] : 0.0;
-        zown_b[r] = (wv == 0 && lane < ncb) ? V.z[r * V.zs + tc + kb + lane] : 0.0;
-    }
-    if (tid == 0) lds_pad[0] = 0.0;
-    stage_l11(tv.S + ka + (size_t)ka * nt, nt, nca, Ls[0]);
-    if (hasb) stage_l11(tv.S + kb + (size_t)kb * nt, nt, ncb, Ls[1]);
-    if (tid < nca) lv[0][tid] = p.live[tc + ka + tid];
-    if (tid < ncb) lv[1][tid] = p.live[tc + kb + tid];
-    const int rowa = ka + (lane < nca ? lane : 0), rowb = kb + (lane < ncb ? lane : ka - kb);
-    double acca[R], accb[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) { acca[r] = 0.0; accb[r] = 0.0; }
-    for (int j = 0; j < a; j++) {
-        const size_t c0 = (size_t)(j * PC + wv * 16) * nt;
-        double ta[16], tb[16];
-#pragma unroll
-        for (int q = 0; q < 16; q++) { ta[q] = tv.S[rowa + c0 + (size_t)q * nt]; tb[q] = tv.S[rowb + c0 + (size_t)q * nt]; }
-        if (wv == 0) {
-            double zj[R];
-            gran_wait<R>(gran + (size_t)j * R * 128, epoch, lane, PC, zj);
-#pragma unroll
-            for (int r = 0; r < R; r++) zb[r][lane] = zj[r];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 16; q++) {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                acca[r] += ta[q] * zb[r][wv * 16 + q];
-                accb[r] += tb[q] * zb[r][wv * 16 + q];
-            }
-        }
-        __syncthreads();
-    }
-    // block b's term of block a (rows of b, columns of a): loaded before a's solve
-    double tba[16];
-    {
-        const size_t c0 = (size_t)(ka + wv * 16) * nt;
-#pragma unroll
-        for (int q = 0; q < 16; q++) tba[q] = tv.S[rowb + c0 + (size_t)q * nt];
-    }
-#pragma unroll
-    for (int r = 0; r < R; r++) red[r][wv][lane] = acca[r];
-    __syncthreads();
-    if (wv == 0) {
-        int bad[R] = {};
-        double zr[R];
-#pragma unroll
-        for (int r = 0; r < R; r++)
-            zr[r] = lane < nca ? zown_a[r] - (((red[r][0][lane] + red[r][1][lane]) + red[r][2][lane]) + red[r][3][lane])
-                               : 0.0;
-        tri_lower<R>(zr, Ls[0], lv[0], nca, eps, bad);
-        if (lane < nca) {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                gran_put(gran + (((size_t)a * R + r) * 64 + lane) * 2, epoch, zr[r]);
-                V.z[r * V.zs + tc + ka + lane] = zr[r];
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < R; r++) zb[r][lane] = lane < nca ? zr[r] : 0.0;
-        flag_bad<R>(p, bad);
-    }
-    if (!hasb) return;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 16; q++) {
-#pragma unroll
-        for (int r = 0; r < R; r++) accb[r] += tba[q] * zb[r][wv * 16 + q];
-    }
-#pragma unroll
-    for (int r = 0; r < R; r++) red[r][wv][lane] = accb[r];
-    __syncthreads();
-    if (wv == 0) {
-        int bad[R] = {};
-        double zr[R];
-#pragma unroll
-        for (int r = 0; r < R; r++)
-            zr[r] = lane < ncb ? zown_b[r] - (((red[r][0][lane] + red[r][1][lane]) + red[r][2][lane]) + red[r][3][lane])
-                               : 0.0;
-        tri_lower<R>(zr, Ls[1], lv[1], ncb, eps, bad);
-        if (lane < ncb) {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                gran_put(gran + (((size_t)b * R + r) * 64 + lane) * 2, epoch, zr[r]);
-                V.z[r * V.zs + tc + kb + lane] = zr[r];
-            }
-        }
-        flag_bad<R>(p, bad);
-    }
-}
-
-// Backward pairs, from the last block: workgroup g owns blocks hi = ntb - 1
-// - 2g and lo = hi - 1 (none for an odd count's first workgroup).
 template <int R>
 __global__ void __launch_bounds__(NT)
 k_tail_bwd_pair(PlanView p, TailView tv, SweepVecs V, const double* __restrict__ epsp, gran_t* __restrict__ gran,
@@ -2223,9 +2111,6 @@ void KktDevice::raise_sweep_lds(bool sync_free) {
                               reinterpret_cast<const void*>(&k_tail_bwd_chain<1>),
                               reinterpret_cast<const void*>(&k_tail_bwd_chain<2>)})
             IPO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kChainLds));
-        for (const void* f : {reinterpret_cast<const void*>(&k_tail_fwd_pair<1>),
-                              reinterpret_cast<const void*>(&k_tail_fwd_pair<2>)})
-            IPO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kPairFwdLds));
         for (const void* f : {reinterpret_cast<const void*>(&k_tail_bwd_pair<1>),
                               reinterpret_cast<const void*>(&k_tail_bwd_pair<2>)})
             IPO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kPairBwdLds));
@@ -2341,10 +2226,7 @@ void KktDevice::sweep(double* dz, const double* epsp) {
             hipLaunchKernelGGL(k_tail_fwd_lead<R>, dim3(grid), dim3(kLeadNT), kChainLds, s, pv, tv, V, epsp,
                                dChainGran_.get(), dChainGran_.get() + static_cast<size_t>(plan_.ntb) * 2 * 128,
                                ++chain_epoch_, dlead_ticket_.get(), tb);
-        } else if (knobs_.chain_pairs)
-            hipLaunchKernelGGL(k_tail_fwd_pair<R>, dim3((plan_.ntb + 1) / 2), dim3(NT), kPairFwdLds, s, pv, tv, V, epsp,
-                               dChainGran_.get(), ++chain_epoch_);
-        else
+        } else
             hipLaunchKernelGGL(k_tail_fwd_chain<R>, dim3(plan_.ntb), dim3(NT), kChainLds, s, pv, tv, V, epsp,
                                dChainGran_.get(), ++chain_epoch_);
 #ifdef IPO_LEAD_STAMPS

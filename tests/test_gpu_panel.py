@@ -117,13 +117,12 @@ def test_hsd_overlap_bitwise():
 
 
 def test_tail_chain_pairs_bitwise():
-    """Dense-tail substitution chains with two 64-row blocks per workgroup
-    (k_tail_fwd_pair / k_tail_bwd_pair, IPO_HIP_CHAIN_PAIRS=1; off by default)
+    """The backward dense-tail substitution chain with two 64-row blocks per
+    workgroup (k_tail_bwd_pair, IPO_HIP_CHAIN_PAIRS=1; off by default)
     against one block per workgroup (IPO_HIP_CHAIN_PAIRS=0): the same
     arithmetic in the same order, the first block's z handed on inside the
     workgroup -- identical dfl001 HSD solves (trace and final values).  The
-    lead forward sweep is off on both sides (IPO_HIP_CHAIN_LEAD=0), since it
-    takes precedence over the forward pair kernel."""
+    forward sweep is the one-block chain on both sides (IPO_HIP_CHAIN_LEAD=0)."""
     off = (("IPO_HIP_CHAIN_LEAD", "0"),)
     assert _solve_env("IPO_HIP_CHAIN_PAIRS", "0", extra=off) == _solve_env("IPO_HIP_CHAIN_PAIRS", "1", extra=off)
 
