@@ -798,7 +798,8 @@ namespace {
 // One integer array of a plan ("plan.<member>") or of its launch schedule
 // (part.member of KktSchedule), pairs and triples flattened
 // (ipo_hip_kkt_schedule).
-std::vector<int> schedule_array(const ipo::KktPlan& P, const ipo::KktSchedule& S, const std::string& name) {
+std::vector<int> schedule_array(const ipo::KktPlan& P, const ipo::KktKnobs& knobs, const ipo::KktSchedule& S,
+                                const std::string& name) {
     using V = std::vector<int>;
     const auto flat2 = [](const std::vector<ipo::SchedInt2>& w) {
         V v;
@@ -856,6 +857,19 @@ std::vector<int> schedule_array(const ipo::KktPlan& P, const ipo::KktSchedule& S
     if (name == "gather.dims") return {one(S.gather.split_cnt), one(S.gather.partial_tiles)};
     if (name == "chunks.dims") return {one(S.chunks.partial_stride)};
     if (name == "work.launches") return {S.work.fwd_launches, S.work.bwd_launches};
+    // the sweeps' step lists, five ints a step (kind, q0, n, a, b); *_blocked:
+    // the blocked tail's rule applied to this plan
+    const auto steps = [](const std::vector<ipo::SweepStep>& w) {
+        V v;
+        for (const ipo::SweepStep& e : w) v.insert(v.end(), {e.kind, e.q0, e.n, e.a, e.b});
+        return v;
+    };
+    if (name == "sweep.fwd") return steps(S.sweep.fwd);
+    if (name == "sweep.bwd") return steps(S.sweep.bwd);
+    if (name == "sweep.fwd_blocked" || name == "sweep.bwd_blocked") {
+        const ipo::SweepSteps b = ipo::build_sweep_steps(P, knobs, S.paths, S.chunks, S.order, S.sf, true);
+        return steps(name == "sweep.fwd_blocked" ? b.fwd : b.bwd);
+    }
     if (name == "tail.visit_list") return V(S.tail.visit_list.begin(), S.tail.visit_list.end());
     if (name == "tail.run_items") {
         V v;
@@ -925,17 +939,18 @@ long ipo_hip_kkt_schedule(int m, int n, const int* kA, const int* iA, int nforce
         ipo::csc_transpose(m, n, kA, iA, a.data(), kat, iat, at);
         const ipo::KktPlan P =
             ipo::build_kkt_plan(m, n, kA, iA, kat.data(), iat.data(), nforced, ipo::device_tail_density());
-        const ipo::KktSchedule S = ipo::build_kkt_schedule(P, ipo::KktKnobs::from_env(), cus);
+        const ipo::KktKnobs knobs = ipo::KktKnobs::from_env();
+        const ipo::KktSchedule S = ipo::build_kkt_schedule(P, knobs, cus);
         // one name: that array; several, comma-separated: each array's length, then its entries
         // (a test reads a whole schedule from one build of the plan)
         const std::string names(name);
         std::vector<int> v;
         if (names.find(',') == std::string::npos) {
-            v = schedule_array(P, S, names);
+            v = schedule_array(P, knobs, S, names);
         } else {
             for (size_t b = 0; b <= names.size();) {
                 const size_t e = std::min(names.find(',', b), names.size());
-                const std::vector<int> w = schedule_array(P, S, names.substr(b, e - b));
+                const std::vector<int> w = schedule_array(P, knobs, S, names.substr(b, e - b));
                 v.push_back(static_cast<int>(w.size()));
                 v.insert(v.end(), w.begin(), w.end());
                 b = e + 1;

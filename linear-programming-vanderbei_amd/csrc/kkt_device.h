@@ -193,8 +193,8 @@ class KktDevice {
                      const std::vector<int>& iat, const std::vector<double>& at, const QBlock* qb);
     void build_panel_units();
     SolveChunks build_solve_chunks();
-    void build_sweep_order(const SolveChunks& ch);
-    void build_sync_free_plan(const SolveChunks& ch, int cus);
+    SweepOrder build_sweep_order(const SolveChunks& ch);
+    void build_sync_free_plan(const SolveChunks& ch, const SweepOrder& so, int cus);
     void build_gather_chunks(const VisitSlots& vs);
     void count_work();
     void build_slot_records(const std::vector<int>& kslot_v);
@@ -215,7 +215,9 @@ class KktDevice {
     TailView tail_view() const;
     template <int R>
     void sweep(double* dz, const double* epsp);   // rawsolve's sweeps, sf_tbase, tail_rhs_*: kkt_sweep.hip
-    void sweep_blocked(double* dz, const double* epsp);
+    // launches one list of h_.sweep in order; returns the kernels it launched
+    template <int R>
+    int run_sweep_steps(const std::vector<SweepStep>& steps, bool forward, double* dz, const double* epsp);
     void tail_rhs_begin(double* dz, int R);
     void tail_rhs_end(double* dz, int R);
     DevBuf<int> dIncons_;          // per right-hand side: inconsistent-system flag

@@ -916,9 +916,9 @@ KktDevice::KktDevice(int m, int n, const int* kA, const int* iA, const double* A
     {
         const SolveChunks ch = build_solve_chunks();     // its per-supernode part, for the next two steps
         mark("build_solve_chunks");
-        build_sweep_order(ch);
+        const SweepOrder so = build_sweep_order(ch);     // its per-level counts, for the sweeps' step lists
         mark("build_sweep_order");
-        build_sync_free_plan(ch, cus);
+        build_sync_free_plan(ch, so, cus);
         mark("build_sync_free_plan");
     }
     const VisitSlots vs = build_visit_slots(plan_, knobs_, h_.paths);
@@ -1019,19 +1019,20 @@ SolveChunks KktDevice::build_solve_chunks() {
     h_.partial_stride = ch.partial_stride;
     dPartial_.alloc(2 * h_.partial_stride);
     IPO_HIP_CHECK(hipStreamSynchronize(s));
-    h_.chunk_ptr = ch.chunk_ptr;
     ch.chunk_sup = {};
     ch.chunk_r0 = {};
     return ch;
 }
 
-void KktDevice::build_sweep_order(const SolveChunks& ch) {
+// The sweep order of every level; returns its per-level leaf counts (the
+// order itself is dropped once uploaded)
+SweepOrder KktDevice::build_sweep_order(const SolveChunks& ch) {
     hipStream_t s = stream_;
     SweepOrder so = ipo::build_sweep_order(plan_, h_.paths, ch);
     dsweep_sups_.upload(so.sweep_sups, s);
     IPO_HIP_CHECK(hipStreamSynchronize(s));
-    h_.leaf_cnt = std::move(so.leaf_cnt);
-    h_.leaf8_cnt = std::move(so.leaf8_cnt);
+    so.sweep_sups = {};
+    return so;
 }
 
 // Gather chunks (split K): groups = sparse levels (with their visits, vs),
@@ -1056,11 +1057,10 @@ void KktDevice::build_gather_chunks(const VisitSlots& vs) {
     h_.ck_wide = std::move(g.ck_wide);
 }
 
-// Launches per sweep and algorithmic work per phase occurrence
+// Algorithmic work per phase occurrence (the sweeps' launches are counted
+// where they are made, run_sweep_steps)
 void KktDevice::count_work() {
-    const WorkCounts w = ipo::count_work(plan_, knobs_, h_.chunk_ptr, h_.leaf_cnt, h_.leaf8_cnt, h_.sf_level);
-    h_.fwd_launches = w.fwd_launches;
-    h_.bwd_launches = w.bwd_launches;
+    const WorkCounts w = ipo::count_work(plan_, knobs_, h_.sweep);
     std::copy(w.flops, w.flops + kNumPhases, work_flops);
     std::copy(w.bytes, w.bytes + kNumPhases, work_bytes);
 }
@@ -1168,9 +1168,10 @@ void KktDevice::alloc_numeric() {
 
 // Sync-free top levels of the sweeps (kkt_schedule.h): the forward update
 // lists (yrow_ptr as the plan's, yrow_idx with the moved slices), the padded
-// slices, the items and their counters.  cus: the device's CU count, the
+// slices, the items and their counters; then, every fact they depend on being
+// known, the sweeps' step lists (h_.sweep).  cus: the device's CU count, the
 // sweeps' grid.
-void KktDevice::build_sync_free_plan(const SolveChunks& ch, int cus) {
+void KktDevice::build_sync_free_plan(const SolveChunks& ch, const SweepOrder& so, int cus) {
     hipStream_t s = stream_;
     dyrow_ptr_.upload(plan_.yrow_ptr, s);
     const SyncFreePlan sf = ipo::build_sync_free_plan(plan_, knobs_, h_.paths, ch);
@@ -1178,7 +1179,6 @@ void KktDevice::build_sync_free_plan(const SolveChunks& ch, int cus) {
     h_.sf_level = sf.sf_level;
     dyrow_idx_.upload(sf.yrow_idx, s);
     dybase_.upload(sf.ybase, s);
-    h_.pre_cols = static_cast<int>(sf.pre_col.size());
     if (sf.late_lists) {
         dylate_ptr_.upload(sf.ylate_ptr, s);
         dylate_idx_.upload(sf.ylate_idx.empty() ? std::vector<int>{0} : sf.ylate_idx, s);
@@ -1189,8 +1189,7 @@ void KktDevice::build_sync_free_plan(const SolveChunks& ch, int cus) {
     }
     h_.ybuf_stride = sf.ybuf_stride;
     dYbuf_.alloc(2 * h_.ybuf_stride);
-    h_.nsf_f = static_cast<int>(sf.items_f.size());
-    h_.nsf_b = static_cast<int>(sf.items_b.size());
+    h_.sweep = build_sweep_steps(plan_, knobs_, h_.paths, ch, so, sf, h_.paths.tail_blocked);
     if (sf.range(plan_)) {
         static_assert(sizeof(SchedInt2) == sizeof(int2), "SchedInt2 is uploaded as int2");
         dsf_items_f_.upload(reinterpret_cast<const int2*>(sf.items_f.data()), sf.items_f.size(), s);

@@ -17,6 +17,7 @@ KktPaths kkt_paths(const KktPlan& P, const KktKnobs& knobs) {
     KktPaths p;
     p.visits = knobs.deep_tree(P.nlevels);
     p.chain_lead = knobs.chain_lead && P.nt > 0 && P.ntb <= kChainMaxBlocks;
+    p.tail_blocked = P.nt > 0 && P.ntb > kChainMaxBlocks;
     p.tail_run = knobs.tail_run && P.nt > 0 && P.ntb <= kTailSchedMaxBlocks;
     p.run_winpub = knobs.tail_winpub && p.tail_run;
     p.small_leaves = knobs.small_leaves < 0 ? kSmallLeafMinCount : knobs.small_leaves;
@@ -111,7 +112,8 @@ SolveChunks build_solve_chunks(const KktPlan& P) {
 
 // Sweep order of each level: on levels without solve chunks the
 // single-column supernodes with <= 64 rows below come first (one wave
-// each, k_fwd_leaf / k_bwd_leaf), the rest after them
+// each, k_fwd_leaf / k_bwd_leaf), the rest after them.  A blocked tail's
+// sweeps take every level by the chunked or the plain kernels: the level order.
 SweepOrder build_sweep_order(const KktPlan& P, const KktPaths& paths, const SolveChunks& ch) {
     SweepOrder r;
     std::vector<int>& ss = r.sweep_sups;
@@ -119,7 +121,7 @@ SweepOrder build_sweep_order(const KktPlan& P, const KktPaths& paths, const Solv
     r.leaf_cnt.assign(P.nlevels, 0);
     r.leaf8_cnt.assign(P.nlevels, 0);
     const int min8 = paths.small_leaves;
-    for (int l = 0; l < P.nlevels; l++) {
+    for (int l = 0; l < P.nlevels && !paths.tail_blocked; l++) {
         if (ch.chunk_ptr[l + 1] > ch.chunk_ptr[l]) continue;
         const auto b = ss.begin() + P.level_ptr[l], e = ss.begin() + P.level_ptr[l + 1];
         const auto mid = std::stable_partition(b, e, [&](int sp) {
@@ -403,24 +405,57 @@ GatherChunks build_gather_chunks(const KktPlan& P, const KktKnobs& knobs, const 
     return r;
 }
 
-// Launches per sweep and algorithmic work per phase occurrence
-WorkCounts count_work(const KktPlan& P, const KktKnobs& knobs, const std::vector<int>& chunk_ptr,
-                      const std::vector<int>& leaf_cnt, const std::vector<int>& leaf8_cnt, int sf_level) {
-    WorkCounts w;
-    w.fwd_launches = w.bwd_launches = sf_level < P.nlevels ? 1 : 0;
-    for (int l = 0; l < sf_level; l++) {
-        const int nsl = P.level_ptr[l + 1] - P.level_ptr[l];
-        const int nl = leaf_cnt[l], n8 = leaf8_cnt[l];
-        const int k = chunk_ptr[l + 1] > chunk_ptr[l] ? 2
-                    : (n8 > 0) + (nl > n8 && nsl > nl && knobs.merge_levels ? 1 : (nl > n8) + (nsl > nl));
-        w.fwd_launches += k;
-        w.bwd_launches += k;
+int sweep_launches(const std::vector<SweepStep>& steps) {
+    int n = 0;
+    for (const SweepStep& st : steps) n += st.kind == kSwChunked ? 2 : 1;
+    return n;
+}
+
+SweepSteps build_sweep_steps(const KktPlan& P, const KktKnobs& knobs, const KktPaths& paths, const SolveChunks& ch,
+                             const SweepOrder& order, const SyncFreePlan& sf, bool blocked) {
+    SweepSteps r;
+    auto level = [&](int l, std::vector<SweepStep>& out) {
+        const int q0 = P.level_ptr[l], q1 = P.level_ptr[l + 1];
+        const int cb = ch.chunk_ptr[l], ce = ch.chunk_ptr[l + 1];
+        if (ce > cb) { out.push_back({kSwChunked, q0, q1 - q0, cb, ce - cb}); return; }
+        const int nl = blocked ? 0 : order.leaf_cnt[l], n8 = blocked ? 0 : order.leaf8_cnt[l];
+        if (n8 > 0) out.push_back({kSwLeaf8, q0, n8, 0, 0});
+        if (nl > n8 && q1 - q0 > nl && knobs.merge_levels) {
+            out.push_back({kSwMerged, q0 + n8, nl - n8, q1 - q0 - nl, 0});
+        } else {
+            if (nl > n8) out.push_back({kSwLeaf, q0 + n8, nl - n8, 0, 0});
+            if (q1 - q0 > nl) out.push_back({kSwPlain, q0 + nl, q1 - q0 - nl, 0, 0});
+        }
+    };
+    const bool range = !blocked && sf.range(P);      // the narrow top levels in one launch
+    const int top = blocked ? P.nlevels : sf.sf_level;
+    const int pre_cols = static_cast<int>(sf.pre_col.size());
+    for (int l = 0; l < top; l++) level(l, r.fwd);
+    if (range) {
+        if (pre_cols > 0) r.fwd.push_back({kSwPre, 0, pre_cols, 0, 0});
+        r.fwd.push_back({kSwSyncFree, 0, static_cast<int>(sf.items_f.size()), pre_cols > 0 || sf.late_lists, 0});
     }
     if (P.nt > 0) {
-        const int chain = P.ntb <= kChainMaxBlocks;
-        w.fwd_launches += 1 + (chain ? 1 : P.ntb);
-        w.bwd_launches += chain ? 1 : 1 + P.ntb;
+        r.fwd.push_back({kSwTailGather, 0, 0, 0, 0});
+        if (blocked) {
+            for (int kb = 0; kb < P.ntb; kb++) r.fwd.push_back({kSwTailBlock, 0, 0, kb, 0});
+            r.bwd.push_back({kSwTailDscale, 0, 0, 0, 0});
+            for (int kb = P.ntb - 1; kb >= 0; kb--) r.bwd.push_back({kSwTailBlock, 0, 0, kb, 0});
+        } else {
+            r.fwd.push_back({paths.chain_lead ? kSwTailLead : kSwTailChain, 0, 0, 0, 0});
+            r.bwd.push_back({knobs.chain_pairs ? kSwTailPair : kSwTailChain, 0, 0, 0, 0});
+        }
     }
+    if (range) r.bwd.push_back({kSwSyncFree, 0, static_cast<int>(sf.items_b.size()), 0, 0});
+    for (int l = top - 1; l >= 0; l--) level(l, r.bwd);
+    return r;
+}
+
+// Launches per sweep and algorithmic work per phase occurrence
+WorkCounts count_work(const KktPlan& P, const KktKnobs& knobs, const SweepSteps& sweep) {
+    WorkCounts w;
+    w.fwd_launches = sweep_launches(sweep.fwd);
+    w.bwd_launches = sweep_launches(sweep.bwd);
     // Bytes: each phase's entries of L read and written once (+ the gather's
     // source reads from the plan)
     double gb = 0;
@@ -719,7 +754,8 @@ KktSchedule build_kkt_schedule(const KktPlan& P, const KktKnobs& knobs, int cus)
     s.sf = build_sync_free_plan(P, knobs, s.paths, s.chunks);
     s.visits = build_visit_slots(P, knobs, s.paths);
     s.gather = build_gather_chunks(P, knobs, s.paths, s.visits);
-    s.work = count_work(P, knobs, s.chunks.chunk_ptr, s.order.leaf_cnt, s.order.leaf8_cnt, s.sf.sf_level);
+    s.sweep = build_sweep_steps(P, knobs, s.paths, s.chunks, s.order, s.sf, s.paths.tail_blocked);
+    s.work = count_work(P, knobs, s.sweep);
     s.usrc = build_task_src(P, P.utasks);
     if (P.nt > 0) s.tsrc = build_task_src(P, P.tail_tasks);
     s.slot_rec = build_slot_records(P, s.paths.visits ? s.visits.kslot : P.kslot, P.utasks);

@@ -7,7 +7,12 @@
 // properties the persistent kernels rely on (an item waits only on items
 // earlier in its list) are tested on the CPU (tests/test_kkt_schedule.py,
 // tests/test_tail_schedule.py).  The dense tail's host schedules live here
-// too.  build_kkt_schedule runs every part in the constructor's order.
+// too, and so does the launch list of a substitution sweep (SweepStep,
+// build_sweep_steps): which kernels a sweep launches, over which ranges and
+// in what order is decided here once, KktDevice::run_sweep_steps
+// (kkt_sweep.hip) walks the list, and the launch counts of the timing mode are
+// the list's totals.  build_kkt_schedule runs every part in the constructor's
+// order.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -43,12 +48,36 @@ struct SchedUint2 { unsigned x, y; };
 struct KktPaths {
     bool visits = false;       // the deep-tree gather schedule and the sweeps' pre-pass
     bool chain_lead = false;   // forward dense-tail sweep by one lead workgroup + helpers (k_tail_fwd_lead)
+    bool tail_blocked = false; // a tail of more than kChainMaxBlocks block columns: per-block sweep launches
     bool tail_run = false;     // the dense tail as one persistent launch (k_tail_run)
     bool run_winpub = false;   // the run's window hand-off (TailRun::pub)
     int small_leaves = 0;      // knobs.small_leaves, unset: kSmallLeafMinCount
     int sf_width = 0;          // widest level of the sync-free range (build_sync_free_plan)
 };
 KktPaths kkt_paths(const KktPlan& P, const KktKnobs& knobs);
+
+// One step of a substitution sweep: a kind and up to four integers.  The
+// level kinds stand in both lists, for their forward kernel(s) in `fwd` and
+// their backward kernel(s) in `bwd`; q0 indexes the sweep order.
+enum SweepKind {
+    kSwChunked = 0,   // k_fwd_diag + k_fwd_gemv / k_bwd_partial + k_bwd_finish: n supernodes from q0, b chunks from a
+    kSwPlain,         // k_forward / k_backward: n supernodes from q0
+    kSwLeaf8,         // k_fwd_leaf8 / k_bwd_leaf8: n small leaves from q0
+    kSwMerged,        // k_fwd_level / k_bwd_level: n leaves from q0, then a other supernodes
+    kSwLeaf,          // k_fwd_leaf / k_bwd_leaf: n leaves from q0
+    kSwPre,           // k_fwd_pre: n columns (deep trees)
+    kSwSyncFree,      // k_fwd_sf / k_bwd_sf: n items; a: the forward launch reads the late lists
+    kSwTailGather,    // k_tail_gather, between tail_rhs_begin and tail_rhs_end
+    kSwTailLead,      // k_tail_fwd_lead
+    kSwTailChain,     // k_tail_fwd_chain / k_tail_bwd_chain
+    kSwTailPair,      // k_tail_bwd_pair
+    kSwTailBlock,     // k_tail_fwd / k_tail_bwd of block column a (blocked tails, one right-hand side)
+    kSwTailDscale,    // k_tail_dscale (blocked tails)
+};
+struct SweepStep { int kind, q0, n, a, b; };
+struct SweepSteps { std::vector<SweepStep> fwd, bwd; };   // in launch order
+// kernel launches of a list: Chunked two, every other step one
+int sweep_launches(const std::vector<SweepStep>& steps);
 
 // What the launch code reads on the host: per-level and per-group pointers
 // and counts, strides and flags.  Everything else a step builds is a local of
@@ -61,15 +90,10 @@ struct KktLaunch {
     std::vector<char> split_level;   // per level: k_diag + k_trsm instead of the fused panels (wide levels)
     std::vector<int> small1_cnt;     // per level: leading single-column small panels of <= 8 rows (k_panel_s1)
     // sweeps
-    std::vector<int> chunk_ptr;      // per level: solve chunks [chunk_ptr[l], chunk_ptr[l+1])
-    std::vector<int> leaf_cnt;       // per level: leading single-column supernodes of the sweep order
-    std::vector<int> leaf8_cnt;      // per level: the first of them, small leaves (k_fwd_leaf8 / k_bwd_leaf8)
+    SweepSteps sweep;                // the launches of a substitution sweep (run_sweep_steps)
     size_t partial_stride = 1;       // backward partial sums of one right-hand side
     int sf_level = 0;                // first level of the sync-free range (nlevels: none)
-    int nsf_f = 0, nsf_b = 0;        // its forward / backward items
-    int pre_cols = 0;                // columns of the deep-tree pre-pass (k_fwd_pre)
     size_t ybuf_stride = 1, zpad_stride = 1;
-    int fwd_launches = 0, bwd_launches = 0;   // kernel launches per substitution sweep
     // gather groups (sparse level l, group nlevels = tail)
     std::vector<int> ck_ptr;         // per group: chunks [ck_ptr[g], ck_ptr[g+1])
     std::vector<int> ck_kind;        // per group: 0 k_update, 1 k_update_flat, 2 k_update_quad
@@ -97,7 +121,8 @@ struct SolveChunks {
 };
 SolveChunks build_solve_chunks(const KktPlan& P);
 
-// level_sups in sweep order (leaves first on unchunked levels)
+// level_sups in sweep order (leaves first on unchunked levels; a blocked
+// tail's sweeps take no leaf kernels: the level order, counts zero)
 struct SweepOrder {
     std::vector<int> sweep_sups;
     std::vector<int> leaf_cnt, leaf8_cnt;
@@ -140,13 +165,24 @@ struct GatherChunks {
 GatherChunks build_gather_chunks(const KktPlan& P, const KktKnobs& knobs, const KktPaths& paths,
                                  const VisitSlots& vs);
 
-// Launches per sweep and algorithmic work per phase occurrence
+// The launches of a substitution sweep.  Forward: levels [0, sf_level)
+// ascending, each as one Chunked step or as Leaf8, then Merged or Leaf and
+// Plain; Pre and SyncFree where a sync-free range exists; on a dense tail
+// TailGather and TailLead or TailChain.  Backward: TailPair or TailChain,
+// SyncFree, the levels descending, each level's steps in their forward order.
+// blocked (paths.tail_blocked; an argument so that tests reach the rule on
+// small plans): every level as Chunked or Plain, no Pre or SyncFree,
+// TailGather and TailBlock 0 .. ntb - 1 forward, TailDscale and TailBlock
+// ntb - 1 .. 0 at the head of the backward list.
+SweepSteps build_sweep_steps(const KktPlan& P, const KktKnobs& knobs, const KktPaths& paths, const SolveChunks& ch,
+                             const SweepOrder& order, const SyncFreePlan& sf, bool blocked);
+
+// Launches per sweep (the step lists' totals) and algorithmic work per phase occurrence
 struct WorkCounts {
     int fwd_launches = 0, bwd_launches = 0;
     double flops[kNumPhases] = {}, bytes[kNumPhases] = {};
 };
-WorkCounts count_work(const KktPlan& P, const KktKnobs& knobs, const std::vector<int>& chunk_ptr,
-                      const std::vector<int>& leaf_cnt, const std::vector<int>& leaf8_cnt, int sf_level);
+WorkCounts count_work(const KktPlan& P, const KktKnobs& knobs, const SweepSteps& sweep);
 
 // Per-task source descriptors and per-slot records of the gather
 std::vector<TaskSrc> build_task_src(const KktPlan& P, const std::vector<TailTask>& ts);
@@ -200,6 +236,7 @@ struct KktSchedule {
     SyncFreePlan sf;
     VisitSlots visits;
     GatherChunks gather;
+    SweepSteps sweep;
     WorkCounts work;
     std::vector<TaskSrc> usrc, tsrc;
     std::vector<SlotRec> slot_rec, tail_slot_rec;

@@ -8,8 +8,11 @@
 #include <array>
 #include <climits>
 #include <cstdio>
+#include <initializer_list>
 #include <map>
+#include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "dev_common.h"
 #include "kkt_device.h"
@@ -2101,23 +2104,25 @@ __global__ void k_scale_scalar(double* e, int n, double f) { if (static_cast<int
 // k_bwd_sf of a plan with a sync-free range; else the dense tail's chain,
 // pair and lead kernels (0 < ntb <= kChainMaxBlocks).
 void KktDevice::raise_sweep_lds(bool sync_free) {
+    struct Lds { const void* f; int bytes; };
+    auto raise = [](std::initializer_list<Lds> table) {
+        for (const Lds& e : table)
+            IPO_HIP_CHECK(hipFuncSetAttribute(e.f, hipFuncAttributeMaxDynamicSharedMemorySize, e.bytes));
+    };
     if (sync_free && h_.sf_level < plan_.nlevels)
-        for (const void* f : {reinterpret_cast<const void*>(&k_fwd_sf<1>), reinterpret_cast<const void*>(&k_fwd_sf<2>),
-                              reinterpret_cast<const void*>(&k_bwd_sf<1>), reinterpret_cast<const void*>(&k_bwd_sf<2>)})
-            IPO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kChainLds));
-    if (!sync_free && plan_.nt > 0 && plan_.ntb <= kChainMaxBlocks) {
-        for (const void* f : {reinterpret_cast<const void*>(&k_tail_fwd_chain<1>),
-                              reinterpret_cast<const void*>(&k_tail_fwd_chain<2>),
-                              reinterpret_cast<const void*>(&k_tail_bwd_chain<1>),
-                              reinterpret_cast<const void*>(&k_tail_bwd_chain<2>)})
-            IPO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kChainLds));
-        for (const void* f : {reinterpret_cast<const void*>(&k_tail_bwd_pair<1>),
-                              reinterpret_cast<const void*>(&k_tail_bwd_pair<2>)})
-            IPO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kPairBwdLds));
-        for (const void* f : {reinterpret_cast<const void*>(&k_tail_fwd_lead<1>),
-                              reinterpret_cast<const void*>(&k_tail_fwd_lead<2>)})
-            IPO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kChainLds));
-    }
+        raise({{reinterpret_cast<const void*>(&k_fwd_sf<1>), kChainLds},
+               {reinterpret_cast<const void*>(&k_fwd_sf<2>), kChainLds},
+               {reinterpret_cast<const void*>(&k_bwd_sf<1>), kChainLds},
+               {reinterpret_cast<const void*>(&k_bwd_sf<2>), kChainLds}});
+    if (!sync_free && plan_.nt > 0 && plan_.ntb <= kChainMaxBlocks)
+        raise({{reinterpret_cast<const void*>(&k_tail_fwd_chain<1>), kChainLds},
+               {reinterpret_cast<const void*>(&k_tail_fwd_chain<2>), kChainLds},
+               {reinterpret_cast<const void*>(&k_tail_bwd_chain<1>), kChainLds},
+               {reinterpret_cast<const void*>(&k_tail_bwd_chain<2>), kChainLds},
+               {reinterpret_cast<const void*>(&k_tail_bwd_pair<1>), kPairBwdLds},
+               {reinterpret_cast<const void*>(&k_tail_bwd_pair<2>), kPairBwdLds},
+               {reinterpret_cast<const void*>(&k_tail_fwd_lead<1>), kChainLds},
+               {reinterpret_cast<const void*>(&k_tail_fwd_lead<2>), kChainLds}});
 }
 
 // Per-level summary of the last forward sync-free sweep's stamps (10 ns
@@ -2160,134 +2165,18 @@ void KktDevice::dump_sf_stamps() const {
 #endif
 }
 
-// Substitution sweeps for R right-hand sides stored at dz + r * K.
+// Substitution sweeps for R right-hand sides stored at dz + r * K: the two
+// step lists of the schedule (h_.sweep, kkt_schedule.h), walked in order.
 template <int R>
 void KktDevice::sweep(double* dz, const double* epsp) {
     hipStream_t s = stream_;
-    const PlanView pv = plan_view();
-    const SweepVecs V{dz, static_cast<size_t>(T_), dYbuf_.get(), h_.ybuf_stride};
-    const size_t ps = h_.partial_stride;
     if (timing_) IPO_HIP_CHECK(hipEventRecord(ev2_, s));
     ph_begin(s);
-    for (int l = 0; l < h_.sf_level; l++) {
-        const int q0 = plan_.level_ptr[l], q1 = plan_.level_ptr[l + 1];
-        const int cb = h_.chunk_ptr[l], ce = h_.chunk_ptr[l + 1];
-        if (ce > cb) {
-            hipLaunchKernelGGL(k_fwd_diag<R>, dim3(q1 - q0), dim3(NT), 0, s, pv, dlevel_sups_.get(), q0,
-                               dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
-            hipLaunchKernelGGL(k_fwd_gemv<R>, dim3(ce - cb), dim3(NT), 0, s, pv, dchunk_sup_.get(), dchunk_r0_.get(), cb,
-                               V);
-        } else {
-            const int nl = h_.leaf_cnt[l], n8 = h_.leaf8_cnt[l];
-            if (n8 > 0)
-                hipLaunchKernelGGL(k_fwd_leaf8<R>, dim3(ceil_div(n8, NT / kSmallLeaf)), dim3(NT), 0, s, pv,
-                                   dsweep_sups_.get(), q0, n8, dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
-            if (nl > n8 && q1 - q0 > nl && knobs_.merge_levels) {
-                const int nlb = ceil_div(nl - n8, NT / 64);
-                hipLaunchKernelGGL(k_fwd_level<R>, dim3(nlb + q1 - q0 - nl), dim3(NT), 0, s, pv, dsweep_sups_.get(),
-                                   q0 + n8, nl - n8, nlb, dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
-            } else {
-                if (nl > n8)
-                    hipLaunchKernelGGL(k_fwd_leaf<R>, dim3(ceil_div(nl - n8, NT / 64)), dim3(NT), 0, s, pv,
-                                       dsweep_sups_.get(), q0 + n8, nl - n8, dyrow_ptr_.get(), dyrow_idx_.get(), V,
-                                       epsp);
-                if (q1 - q0 > nl)
-                    hipLaunchKernelGGL(k_forward<R>, dim3(q1 - q0 - nl), dim3(NT), 0, s, pv, dsweep_sups_.get(),
-                                       q0 + nl, dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
-            }
-        }
-    }
-    if (h_.sf_level < plan_.nlevels) {      // the narrow top levels in one launch
-        const SfView sf{dsf_items_f_.get(), h_.nsf_f, dsf_fcnt_.get(), dsf_fflag_.get(), dsf_need_.get(), dsf_par_.get(),
-                        dsf_zbase_.get(), dsf_zpi_.get(), dZpad_.get(), h_.zpad_stride, ++sf_fwd_epoch_,
-                        dsf_ticket_.get(), sf_tbase(0, h_.nsf_f)};
-        const bool pre = h_.pre_cols > 0 || dylate_ptr_.get();
-        if (h_.pre_cols > 0)
-            hipLaunchKernelGGL(k_fwd_pre<R>, dim3(ceil_div(h_.pre_cols, NT)), dim3(NT), 0, s, h_.pre_cols, dpre_col_.get(),
-                               dpre_ptr_.get(), dpre_idx_.get(), V);
-        hipLaunchKernelGGL(k_fwd_sf<R>, dim3(std::min(sf_grid_, h_.nsf_f)), dim3(NT), kChainLds, s, pv, sf,
-                           pre ? dylate_ptr_.get() : dyrow_ptr_.get(), pre ? dylate_idx_.get() : dyrow_idx_.get(),
-                           dchunk_r0_.get(), V, epsp);
-    }
-    if (plan_.nt > 0) {
-        const TailView tv = tail_view();
-        tail_rhs_begin(dz, R);
-        hipLaunchKernelGGL(k_tail_gather<R>, dim3(ceil_div(plan_.nt, 4)), dim3(NT), 0, s, tv, dyrow_ptr_.get(),
-                           dyrow_idx_.get(), V);
-        tail_rhs_end(dz, R);
-        if (h_.paths.chain_lead) {
-            const int grid = 1 + std::max(0, plan_.ntb - 1 - kLeadBlocks);
-            if (lead_ticket_next_ + grid > (1LL << 30)) {
-                IPO_HIP_CHECK(hipMemsetAsync(dlead_ticket_.get(), 0, sizeof(int), s));
-                lead_ticket_next_ = 0;
-            }
-            const int tb = static_cast<int>(lead_ticket_next_);
-            lead_ticket_next_ += grid;
-            hipLaunchKernelGGL(k_tail_fwd_lead<R>, dim3(grid), dim3(kLeadNT), kChainLds, s, pv, tv, V, epsp,
-                               dChainGran_.get(), dChainGran_.get() + static_cast<size_t>(plan_.ntb) * 2 * 128,
-                               ++chain_epoch_, dlead_ticket_.get(), tb);
-        } else
-            hipLaunchKernelGGL(k_tail_fwd_chain<R>, dim3(plan_.ntb), dim3(NT), kChainLds, s, pv, tv, V, epsp,
-                               dChainGran_.get(), ++chain_epoch_);
-#ifdef IPO_LEAD_STAMPS
-        if (h_.paths.chain_lead && chain_epoch_ % 64 == 41) {
-            double st[8][4];
-            IPO_HIP_CHECK(hipStreamSynchronize(s));
-            IPO_HIP_CHECK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_lead_stats), sizeof(st)));
-            std::fprintf(stderr, "lead R %d ntb %d per step us: solver wait-A %.3f tri %.3f wait-B %.3f\n", R, plan_.ntb,
-                         st[0][0], st[0][1], st[0][2]);
-            for (int w = 1; w <= 4; w++)
-                std::fprintf(stderr, "  wave %d: partial wait %.3f (%g polls) phase3 %.3f loads %.3f\n", w, st[w][0],
-                             st[w][1], st[w][2], st[w][3]);
-        }
-#endif
-    }
-    ph_end(kPhForward, h_.fwd_launches, s);
+    const int nf = run_sweep_steps<R>(h_.sweep.fwd, true, dz, epsp);
+    ph_end(kPhForward, nf, s);
     ph_begin(s);
-    if (plan_.nt > 0) {
-        const TailView tv = tail_view();
-        if (knobs_.chain_pairs)
-            hipLaunchKernelGGL(k_tail_bwd_pair<R>, dim3((plan_.ntb + 1) / 2), dim3(NT), kPairBwdLds, s, pv, tv, V, epsp,
-                               dChainGran_.get(), ++chain_epoch_);
-        else
-            hipLaunchKernelGGL(k_tail_bwd_chain<R>, dim3(plan_.ntb), dim3(NT), kChainLds, s, pv, tv, V, epsp,
-                               dChainGran_.get(), ++chain_epoch_);
-    }
-    if (h_.sf_level < plan_.nlevels) {
-        const SfView sf{dsf_items_b_.get(), h_.nsf_b, dsf_bcnt_.get(), dsf_bflag_.get(), dsf_need_.get(), dsf_par_.get(),
-                        dsf_zbase_.get(), dsf_zpi_.get(), dZpad_.get(), h_.zpad_stride, ++sf_bwd_epoch_,
-                        dsf_ticket_.get() + 1, sf_tbase(1, h_.nsf_b)};
-        hipLaunchKernelGGL(k_bwd_sf<R>, dim3(std::min(sf_grid_, h_.nsf_b)), dim3(NT), kChainLds, s, pv, sf,
-                           dchunk_r0_.get(), dsup_chunk0_.get(), dPartial_.get(), ps, V, epsp);
-    }
-    for (int l = h_.sf_level - 1; l >= 0; l--) {
-        const int q0 = plan_.level_ptr[l], q1 = plan_.level_ptr[l + 1];
-        const int cb = h_.chunk_ptr[l], ce = h_.chunk_ptr[l + 1];
-        if (ce > cb) {
-            hipLaunchKernelGGL(k_bwd_partial<R>, dim3(ce - cb), dim3(NT), 0, s, pv, dchunk_sup_.get(), dchunk_r0_.get(),
-                               cb, V, dPartial_.get(), ps);
-            hipLaunchKernelGGL(k_bwd_finish<R>, dim3(q1 - q0), dim3(NT), 0, s, pv, dlevel_sups_.get(), q0,
-                               dsup_chunk0_.get(), dPartial_.get(), ps, V, epsp);
-        } else {
-            const int nl = h_.leaf_cnt[l], n8 = h_.leaf8_cnt[l];
-            if (n8 > 0)
-                hipLaunchKernelGGL(k_bwd_leaf8<R>, dim3(ceil_div(n8, NT / kSmallLeaf)), dim3(NT), 0, s, pv,
-                                   dsweep_sups_.get(), q0, n8, V, epsp);
-            if (nl > n8 && q1 - q0 > nl && knobs_.merge_levels) {
-                const int nlb = ceil_div(nl - n8, NT / 64);
-                hipLaunchKernelGGL(k_bwd_level<R>, dim3(nlb + q1 - q0 - nl), dim3(NT), 0, s, pv, dsweep_sups_.get(),
-                                   q0 + n8, nl - n8, nlb, V, epsp);
-            } else {
-                if (nl > n8)
-                    hipLaunchKernelGGL(k_bwd_leaf<R>, dim3(ceil_div(nl - n8, NT / 64)), dim3(NT), 0, s, pv,
-                                       dsweep_sups_.get(), q0 + n8, nl - n8, V, epsp);
-                if (q1 - q0 > nl)
-                    hipLaunchKernelGGL(k_backward<R>, dim3(q1 - q0 - nl), dim3(NT), 0, s, pv, dsweep_sups_.get(),
-                                       q0 + nl, V, epsp);
-            }
-        }
-    }
-    ph_end(kPhBackward, h_.bwd_launches, s);
+    const int nb = run_sweep_steps<R>(h_.sweep.bwd, false, dz, epsp);
+    ph_end(kPhBackward, nb, s);
     IPO_HIP_CHECK(hipGetLastError());
     if (timing_) {
         IPO_HIP_CHECK(hipEventRecord(ev3_, s));
@@ -2299,6 +2188,165 @@ void KktDevice::sweep(double* dz, const double* epsp) {
         tm_.phase_count[kPhForward]++;
         tm_.phase_count[kPhBackward]++;
     }
+}
+
+// One list of a sweep: every step launches its forward or its backward
+// kernel(s) over the range it carries (SweepKind, kkt_schedule.h) and does the
+// host bookkeeping that goes with that launch.  Returns the kernels launched,
+// counted here and not taken from the schedule.  The TailBlock and TailDscale
+// kernels take one right-hand side: a blocked tail's lists run with R = 1.
+// The cases stand in SweepKind's order, which is also the order the compiler
+// emits the kernel instances in; k_fwd_level<1> and k_fwd_leaf<1> get their
+// address arithmetic scheduled differently unless k_forward<1> is emitted
+// before them, so Plain stays ahead of the leaf kinds (device code compared
+// across changes stays identical).
+template <int R>
+int KktDevice::run_sweep_steps(const std::vector<SweepStep>& steps, bool forward, double* dz, const double* epsp) {
+    hipStream_t s = stream_;
+    const PlanView pv = plan_view();
+    const TailView tv = tail_view();
+    const SweepVecs V{dz, static_cast<size_t>(T_), dYbuf_.get(), h_.ybuf_stride};
+    const size_t ps = h_.partial_stride;
+    const int nt = plan_.nt;
+    int launched = 0;
+    for (const SweepStep& step : steps) {
+        const int q0 = step.q0, n = step.n;
+        switch (step.kind) {
+        case kSwChunked: {
+            const int cb = step.a, nch = step.b;
+            if (forward) {
+                hipLaunchKernelGGL(k_fwd_diag<R>, dim3(n), dim3(NT), 0, s, pv, dsweep_sups_.get(), q0, dyrow_ptr_.get(),
+                                   dyrow_idx_.get(), V, epsp);
+                hipLaunchKernelGGL(k_fwd_gemv<R>, dim3(nch), dim3(NT), 0, s, pv, dchunk_sup_.get(), dchunk_r0_.get(),
+                                   cb, V);
+            } else {
+                hipLaunchKernelGGL(k_bwd_partial<R>, dim3(nch), dim3(NT), 0, s, pv, dchunk_sup_.get(), dchunk_r0_.get(),
+                                   cb, V, dPartial_.get(), ps);
+                hipLaunchKernelGGL(k_bwd_finish<R>, dim3(n), dim3(NT), 0, s, pv, dsweep_sups_.get(), q0,
+                                   dsup_chunk0_.get(), dPartial_.get(), ps, V, epsp);
+            }
+            launched++;      // two kernels
+            break;
+        }
+        case kSwPlain:
+            if (forward)
+                hipLaunchKernelGGL(k_forward<R>, dim3(n), dim3(NT), 0, s, pv, dsweep_sups_.get(), q0, dyrow_ptr_.get(),
+                                   dyrow_idx_.get(), V, epsp);
+            else
+                hipLaunchKernelGGL(k_backward<R>, dim3(n), dim3(NT), 0, s, pv, dsweep_sups_.get(), q0, V, epsp);
+            break;
+        case kSwLeaf8:
+            if (forward)
+                hipLaunchKernelGGL(k_fwd_leaf8<R>, dim3(ceil_div(n, NT / kSmallLeaf)), dim3(NT), 0, s, pv,
+                                   dsweep_sups_.get(), q0, n, dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
+            else
+                hipLaunchKernelGGL(k_bwd_leaf8<R>, dim3(ceil_div(n, NT / kSmallLeaf)), dim3(NT), 0, s, pv,
+                                   dsweep_sups_.get(), q0, n, V, epsp);
+            break;
+        case kSwMerged: {
+            const int nlb = ceil_div(n, NT / 64);
+            if (forward)
+                hipLaunchKernelGGL(k_fwd_level<R>, dim3(nlb + step.a), dim3(NT), 0, s, pv, dsweep_sups_.get(), q0, n,
+                                   nlb, dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
+            else
+                hipLaunchKernelGGL(k_bwd_level<R>, dim3(nlb + step.a), dim3(NT), 0, s, pv, dsweep_sups_.get(), q0, n,
+                                   nlb, V, epsp);
+            break;
+        }
+        case kSwLeaf:
+            if (forward)
+                hipLaunchKernelGGL(k_fwd_leaf<R>, dim3(ceil_div(n, NT / 64)), dim3(NT), 0, s, pv, dsweep_sups_.get(),
+                                   q0, n, dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
+            else
+                hipLaunchKernelGGL(k_bwd_leaf<R>, dim3(ceil_div(n, NT / 64)), dim3(NT), 0, s, pv, dsweep_sups_.get(),
+                                   q0, n, V, epsp);
+            break;
+        case kSwPre:
+            hipLaunchKernelGGL(k_fwd_pre<R>, dim3(ceil_div(n, NT)), dim3(NT), 0, s, n, dpre_col_.get(), dpre_ptr_.get(),
+                               dpre_idx_.get(), V);
+            break;
+        case kSwSyncFree:      // the narrow top levels in one launch
+            if (forward) {
+                const SfView sf{dsf_items_f_.get(), n, dsf_fcnt_.get(), dsf_fflag_.get(), dsf_need_.get(),
+                                dsf_par_.get(), dsf_zbase_.get(), dsf_zpi_.get(), dZpad_.get(), h_.zpad_stride,
+                                ++sf_fwd_epoch_, dsf_ticket_.get(), sf_tbase(0, n)};
+                const bool pre = step.a != 0;
+                hipLaunchKernelGGL(k_fwd_sf<R>, dim3(std::min(sf_grid_, n)), dim3(NT), kChainLds, s, pv, sf,
+                                   pre ? dylate_ptr_.get() : dyrow_ptr_.get(),
+                                   pre ? dylate_idx_.get() : dyrow_idx_.get(), dchunk_r0_.get(), V, epsp);
+            } else {
+                const SfView sf{dsf_items_b_.get(), n, dsf_bcnt_.get(), dsf_bflag_.get(), dsf_need_.get(),
+                                dsf_par_.get(), dsf_zbase_.get(), dsf_zpi_.get(), dZpad_.get(), h_.zpad_stride,
+                                ++sf_bwd_epoch_, dsf_ticket_.get() + 1, sf_tbase(1, n)};
+                hipLaunchKernelGGL(k_bwd_sf<R>, dim3(std::min(sf_grid_, n)), dim3(NT), kChainLds, s, pv, sf,
+                                   dchunk_r0_.get(), dsup_chunk0_.get(), dPartial_.get(), ps, V, epsp);
+            }
+            break;
+        case kSwTailGather:
+            tail_rhs_begin(dz, R);
+            hipLaunchKernelGGL(k_tail_gather<R>, dim3(ceil_div(nt, 4)), dim3(NT), 0, s, tv, dyrow_ptr_.get(),
+                               dyrow_idx_.get(), V);
+            tail_rhs_end(dz, R);
+            break;
+        case kSwTailLead: {
+            const int grid = 1 + std::max(0, plan_.ntb - 1 - kLeadBlocks);
+            if (lead_ticket_next_ + grid > (1LL << 30)) {
+                IPO_HIP_CHECK(hipMemsetAsync(dlead_ticket_.get(), 0, sizeof(int), s));
+                lead_ticket_next_ = 0;
+            }
+            const int tb = static_cast<int>(lead_ticket_next_);
+            lead_ticket_next_ += grid;
+            hipLaunchKernelGGL(k_tail_fwd_lead<R>, dim3(grid), dim3(kLeadNT), kChainLds, s, pv, tv, V, epsp,
+                               dChainGran_.get(), dChainGran_.get() + static_cast<size_t>(plan_.ntb) * 2 * 128,
+                               ++chain_epoch_, dlead_ticket_.get(), tb);
+#ifdef IPO_LEAD_STAMPS
+            if (chain_epoch_ % 64 == 41) {
+                double st[8][4];
+                IPO_HIP_CHECK(hipStreamSynchronize(s));
+                IPO_HIP_CHECK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_lead_stats), sizeof(st)));
+                std::fprintf(stderr, "lead R %d ntb %d per step us: solver wait-A %.3f tri %.3f wait-B %.3f\n", R,
+                             plan_.ntb, st[0][0], st[0][1], st[0][2]);
+                for (int w = 1; w <= 4; w++)
+                    std::fprintf(stderr, "  wave %d: partial wait %.3f (%g polls) phase3 %.3f loads %.3f\n", w,
+                                 st[w][0], st[w][1], st[w][2], st[w][3]);
+            }
+#endif
+            break;
+        }
+        case kSwTailChain:
+            if (forward)
+                hipLaunchKernelGGL(k_tail_fwd_chain<R>, dim3(plan_.ntb), dim3(NT), kChainLds, s, pv, tv, V, epsp,
+                                   dChainGran_.get(), ++chain_epoch_);
+            else
+                hipLaunchKernelGGL(k_tail_bwd_chain<R>, dim3(plan_.ntb), dim3(NT), kChainLds, s, pv, tv, V, epsp,
+                                   dChainGran_.get(), ++chain_epoch_);
+            break;
+        case kSwTailPair:
+            hipLaunchKernelGGL(k_tail_bwd_pair<R>, dim3((plan_.ntb + 1) / 2), dim3(NT), kPairBwdLds, s, pv, tv, V, epsp,
+                               dChainGran_.get(), ++chain_epoch_);
+            break;
+        case kSwTailBlock: {
+            const int kb = step.a;
+            if (forward) {
+                const int below = nt - std::min(nt, (kb + 1) * kPanelCols);
+                hipLaunchKernelGGL(k_tail_fwd, dim3(std::max(1, ceil_div(below, 64))), dim3(NT), 0, s, pv, tv, kb, dz,
+                                   epsp);
+            } else {
+                const int left = kb * kPanelCols;
+                hipLaunchKernelGGL(k_tail_bwd, dim3(std::max(1, ceil_div(left, 64))), dim3(NT), 0, s, pv, tv, kb, dz,
+                                   epsp);
+            }
+            break;
+        }
+        case kSwTailDscale:
+            hipLaunchKernelGGL(k_tail_dscale, dim3(ceil_div(nt, NT)), dim3(NT), 0, s, pv, tv, dz, epsp);
+            break;
+        default:
+            throw std::logic_error("sweep: unknown step kind");
+        }
+        launched++;
+    }
+    return launched;
 }
 
 // Ticket base of the next sync-free launch of direction d over nitems items:
@@ -2313,56 +2361,6 @@ int KktDevice::sf_tbase(int d, int nitems) {
     const int base = static_cast<int>(sf_ticket_next_[d]);
     sf_ticket_next_[d] += draw;
     return base;
-}
-
-// Very large dense tails (more blocks than the chain kernels keep resident):
-// one right-hand side, per-block launches.
-void KktDevice::sweep_blocked(double* dz, const double* epsp) {
-    hipStream_t s = stream_;
-    const PlanView pv = plan_view();
-    const SweepVecs V{dz, static_cast<size_t>(T_), dYbuf_.get(), h_.ybuf_stride};
-    const size_t ps = h_.partial_stride;
-    for (int l = 0; l < plan_.nlevels; l++) {
-        const int q0 = plan_.level_ptr[l], q1 = plan_.level_ptr[l + 1];
-        const int cb = h_.chunk_ptr[l], ce = h_.chunk_ptr[l + 1];
-        if (ce > cb) {
-            hipLaunchKernelGGL(k_fwd_diag<1>, dim3(q1 - q0), dim3(NT), 0, s, pv, dlevel_sups_.get(), q0,
-                               dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
-            hipLaunchKernelGGL(k_fwd_gemv<1>, dim3(ce - cb), dim3(NT), 0, s, pv, dchunk_sup_.get(), dchunk_r0_.get(), cb,
-                               V);
-        } else {
-            hipLaunchKernelGGL(k_forward<1>, dim3(q1 - q0), dim3(NT), 0, s, pv, dlevel_sups_.get(), q0,
-                               dyrow_ptr_.get(), dyrow_idx_.get(), V, epsp);
-        }
-    }
-    const TailView tv = tail_view();
-    const int nt = plan_.nt;
-    tail_rhs_begin(dz, 1);
-    hipLaunchKernelGGL(k_tail_gather<1>, dim3(ceil_div(nt, 4)), dim3(NT), 0, s, tv, dyrow_ptr_.get(), dyrow_idx_.get(),
-                       V);
-    tail_rhs_end(dz, 1);
-    for (int kb = 0; kb < plan_.ntb; kb++) {
-        const int below = nt - std::min(nt, (kb + 1) * kPanelCols);
-        hipLaunchKernelGGL(k_tail_fwd, dim3(std::max(1, ceil_div(below, 64))), dim3(NT), 0, s, pv, tv, kb, dz, epsp);
-    }
-    hipLaunchKernelGGL(k_tail_dscale, dim3(ceil_div(nt, NT)), dim3(NT), 0, s, pv, tv, dz, epsp);
-    for (int kb = plan_.ntb - 1; kb >= 0; kb--) {
-        const int left = kb * kPanelCols;
-        hipLaunchKernelGGL(k_tail_bwd, dim3(std::max(1, ceil_div(left, 64))), dim3(NT), 0, s, pv, tv, kb, dz, epsp);
-    }
-    for (int l = plan_.nlevels - 1; l >= 0; l--) {
-        const int q0 = plan_.level_ptr[l], q1 = plan_.level_ptr[l + 1];
-        const int cb = h_.chunk_ptr[l], ce = h_.chunk_ptr[l + 1];
-        if (ce > cb) {
-            hipLaunchKernelGGL(k_bwd_partial<1>, dim3(ce - cb), dim3(NT), 0, s, pv, dchunk_sup_.get(), dchunk_r0_.get(),
-                               cb, V, dPartial_.get(), ps);
-            hipLaunchKernelGGL(k_bwd_finish<1>, dim3(q1 - q0), dim3(NT), 0, s, pv, dlevel_sups_.get(), q0,
-                               dsup_chunk0_.get(), dPartial_.get(), ps, V, epsp);
-        } else {
-            hipLaunchKernelGGL(k_backward<1>, dim3(q1 - q0), dim3(NT), 0, s, pv, dlevel_sups_.get(), q0, V, epsp);
-        }
-    }
-    IPO_HIP_CHECK(hipGetLastError());
 }
 
 // Sharded sweeps: the tail rows' right-hand side enters once (shard 0), and
@@ -2391,12 +2389,10 @@ void KktDevice::rawsolve(double* dz, int R) {
     } else if (!eps_cleared_) {
         IPO_HIP_CHECK(hipMemsetAsync(epsp, 0, R * sizeof(double), s));
     }
-    if (plan_.nt > 0 && plan_.ntb > kChainMaxBlocks) {
-        for (int r = 0; r < R; r++) sweep_blocked(dz + (size_t)r * T_, epsp + r);
-    } else if (R == 2) {
+    if (R == 2 && !h_.paths.tail_blocked) {
         sweep<2>(dz, epsp);
-    } else {
-        sweep<1>(dz, epsp);
+    } else {                         // (a blocked tail's per-block kernels: one right-hand side at a time)
+        for (int r = 0; r < R; r++) sweep<1>(dz + (size_t)r * T_, epsp + r);
     }
     tm_.rawsolves += R;
 }

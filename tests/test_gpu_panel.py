@@ -302,3 +302,24 @@ def test_merged_level_sweeps_bitwise():
     (IPO_HIP_MERGE_LEVELS=0): the same bodies, so identical dfl001 HSD solves
     (trace and final values)."""
     assert _solve_env("IPO_HIP_MERGE_LEVELS", "0") == _solve_env("IPO_HIP_MERGE_LEVELS", "1")
+
+
+@pytest.mark.parametrize("sf", [None, "0"])
+@pytest.mark.parametrize("name", ["afiro", "25fv47", "pds-02"])
+def test_sweep_launches_are_the_step_lists(name, sf, monkeypatch):
+    """The kernels a substitution sweep launches, counted by the walk over the
+    step lists itself (phase_launches in timing mode), against the totals of
+    the lists as the host-only schedule builds them (work.launches): a step
+    skipped or launched twice shows.  Between them the problems hold every
+    level kind but the small leaves, a sync-free range and a 7-block tail;
+    IPO_HIP_SF=0 sends every level through its own launches."""
+    if sf is None:
+        monkeypatch.delenv("IPO_HIP_SF", raising=False)
+    else:
+        monkeypatch.setenv("IPO_HIP_SF", sf)
+    p = ipo_amd.load_mps(mps_path(name))
+    fwd, bwd = (int(x) for x in ipo_amd.kkt_schedule(p.m, p.n, p.kA, p.iA, "work.launches"))
+    s = ipo_amd.solver(p, "hsd", timing=True)["stats"]
+    assert s["phase_count"][4] > 0 and s["phase_count"][5] == s["phase_count"][4]
+    assert s["phase_launches"][4] == s["phase_count"][4] * fwd
+    assert s["phase_launches"][5] == s["phase_count"][5] * bwd

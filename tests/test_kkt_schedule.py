@@ -21,7 +21,11 @@ kernels (kkt_device.hip):
 The gather (k_update*) has no waits between chunks, but a unit's tile is the
 sum over its k-slots: a slot in two chunks or in none is a silently wrong
 factor, and the split units' partial tiles and arrival counters are indexed
-by ck_part / ck_q."""
+by ck_part / ck_q.
+A substitution sweep launches the two step lists of the schedule in order
+(sweep.fwd, sweep.bwd; KktDevice::run_sweep_steps walks them): the rule that
+picks a level's kernels, the lists' order and their launch totals are checked
+here, the totals also against the counts of the commit before the lists."""
 import os
 import sys
 
@@ -51,7 +55,15 @@ NAMES = [
     "gather.ck_u", "gather.ck_b", "gather.ck_e", "gather.ck_part", "gather.ck_q", "gather.sp_u", "gather.sp_p0",
     "gather.sp_n", "gather.ck_ptr", "gather.sp_ptr", "gather.ck_kind", "gather.dims",
     "tail.visit_list", "tail.visit_ptr", "tail.run_items", "tail.run_ptr",
+    "sweep.fwd", "sweep.bwd", "sweep.fwd_blocked", "sweep.bwd_blocked", "work.launches",
 ]
+# SweepKind (kkt_schedule.h); a step is (kind, q0, n, a, b)
+(CHUNKED, PLAIN, LEAF8, MERGED, LEAF, PRE, SYNC_FREE, TAIL_GATHER, TAIL_LEAD, TAIL_CHAIN, TAIL_PAIR, TAIL_BLOCK,
+ TAIL_DSCALE) = range(13)
+LEVEL_KINDS = (CHUNKED, PLAIN, LEAF8, MERGED, LEAF)
+# the knobs the sweeps' step lists depend on
+SWEEP_KNOBS = ("IPO_HIP_VISITS", "IPO_HIP_MERGE_LEVELS", "IPO_HIP_SMALL_LEAVES", "IPO_HIP_SF", "IPO_HIP_CHAIN_PAIRS",
+               "IPO_HIP_CHAIN_LEAD")
 
 
 class Sched:
@@ -60,7 +72,7 @@ class Sched:
         d = ipo_amd.kkt_schedule(p.m, p.n, p.kA, p.iA, NAMES, cus=cus)
         self.a = {k: v.astype(np.int64) for k, v in d.items()}
         self.T, self.nsup, self.nlevels, self.tail_c0, self.nt, self.ntb = (int(x) for x in self.a["plan.dims"])
-        (self.visits, _, _, _, self.small_leaves, _) = (int(x) for x in self.a["paths"])
+        (self.visits, self.chain_lead, _, _, self.small_leaves, _) = (int(x) for x in self.a["paths"])
         self.sf_level, self.ybuf_stride, self.zpad_stride, self.late_lists = (int(x) for x in self.a["sf.dims"])
         self.nc = np.diff(self.a["plan.col0"])
         self.hb = np.diff(self.a["plan.rowptr"])
@@ -80,12 +92,17 @@ class Sched:
         return np.searchsorted(self["plan.rowptr"], idx, side="right") - 1
 
 
-def load(name, cus, visits, monkeypatch):
-    if visits:
-        monkeypatch.setenv("IPO_HIP_VISITS", "1")
-    else:
-        monkeypatch.delenv("IPO_HIP_VISITS", raising=False)
+def load_env(name, cus, env, monkeypatch):
+    """the schedule with exactly the knobs of env set among SWEEP_KNOBS"""
+    for k in SWEEP_KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
     return Sched(name, cus)
+
+
+def load(name, cus, visits, monkeypatch):
+    return load_env(name, cus, {"IPO_HIP_VISITS": "1"} if visits else {}, monkeypatch)
 
 
 # ------------------------------------------------------------ sync-free plan
@@ -348,6 +365,97 @@ def check_tail_lists(S, cus):
     assert len(y) - sum(gp) == len(vl) or cus < 256, "the run's visits are the steps' at equal chunks"
 
 
+# ------------------------------------------------------- the sweeps' step lists
+def steps_of(S, key):
+    return [tuple(r) for r in S[key].reshape(-1, 5).tolist()]
+
+
+def launches(steps):
+    return sum(2 if st[0] == CHUNKED else 1 for st in steps)
+
+
+def by_level(S, steps):
+    """consecutive level steps grouped by the level their q0 lies in: [(level, [steps])]"""
+    lp = S["plan.level_ptr"]
+    out = []
+    for st in steps:
+        assert st[0] in LEVEL_KINDS, st
+        l = int(np.searchsorted(lp, st[1], side="right")) - 1
+        if not out or out[-1][0] != l:
+            out.append((l, []))
+        out[-1][1].append(st)
+    return out
+
+
+def check_sweep_steps(S, merge=True, pairs=False):
+    """sweep.fwd / sweep.bwd: the rule of every level, the order of the lists, their totals"""
+    lp, cp = S["plan.level_ptr"], S["chunks.chunk_ptr"]
+    nl, n8 = S["order.leaf_cnt"], S["order.leaf8_cnt"]
+    fwd, bwd = steps_of(S, "sweep.fwd"), steps_of(S, "sweep.bwd")
+    nlev_f = next((i for i, st in enumerate(fwd) if st[0] not in LEVEL_KINDS), len(fwd))
+    head_b = next((i for i, st in enumerate(bwd) if st[0] in LEVEL_KINDS), len(bwd))
+    lev_f, lev_b = by_level(S, fwd[:nlev_f]), by_level(S, bwd[head_b:])
+    # levels [0, sf_level) ascending / descending, a level's steps the same in both
+    assert [l for l, _ in lev_f] == list(range(S.sf_level))
+    assert lev_b == lev_f[::-1]
+    for l, steps in lev_f:
+        q0, q1 = int(lp[l]), int(lp[l + 1])
+        # the ranges partition the level in order
+        pos = q0
+        for kind, q, n, a, b in steps:
+            assert q == pos and n > 0, (l, steps)
+            pos += n + (a if kind == MERGED else 0)
+        assert pos == q1, (l, steps)
+        assert (sum(st[0] == CHUNKED for st in steps) == 1) == bool(S.chunked_level(l)), (l, steps)
+        if S.chunked_level(l):
+            assert steps == [(CHUNKED, q0, q1 - q0, int(cp[l]), int(cp[l + 1] - cp[l]))], (l, steps)
+            continue
+        k, k8 = int(nl[l]), int(n8[l])
+        want = [(LEAF8, q0, k8, 0, 0)] if k8 > 0 else []
+        if merge and k > k8 and q1 - q0 > k:
+            want.append((MERGED, q0 + k8, k - k8, q1 - q0 - k, 0))
+        else:
+            if k > k8:
+                want.append((LEAF, q0 + k8, k - k8, 0, 0))
+            if q1 - q0 > k:
+                want.append((PLAIN, q0 + k, q1 - q0 - k, 0, 0))
+        assert steps == want, (l, steps, want)
+    # after the forward levels: pre-pass and sync-free range, then the tail; mirrored backward
+    npre, late = len(S["sf.pre_col"]), int(late_lists_read(S))
+    rng = S.sf_level < S.nlevels
+    want_f = [(PRE, 0, npre, 0, 0)] if npre > 0 else []
+    want_b = []
+    if S.nt > 0:
+        want_b.append((TAIL_PAIR if pairs else TAIL_CHAIN, 0, 0, 0, 0))
+    if rng:
+        want_f.append((SYNC_FREE, 0, len(S["sf.items_f"]) // 2, late, 0))
+        want_b.append((SYNC_FREE, 0, len(S["sf.items_b"]) // 2, 0, 0))
+    if S.nt > 0:
+        want_f += [(TAIL_GATHER, 0, 0, 0, 0), (TAIL_LEAD if S.chain_lead else TAIL_CHAIN, 0, 0, 0, 0)]
+    assert not npre or rng, "a pre-pass without a range"
+    assert fwd[nlev_f:] == want_f, (fwd[nlev_f:], want_f)
+    assert bwd[:head_b] == want_b, (bwd[:head_b], want_b)
+    assert list(S["work.launches"]) == [launches(fwd), launches(bwd)]
+
+
+def late_lists_read(S):
+    """the forward sync-free launch reads the late lists"""
+    return len(S["sf.pre_col"]) > 0 or S.late_lists == 1
+
+
+def check_blocked_steps(S):
+    """sweep.*_blocked: the blocked tail's rule applied to this plan"""
+    lp, cp = S["plan.level_ptr"], S["chunks.chunk_ptr"]
+    fwd, bwd = steps_of(S, "sweep.fwd_blocked"), steps_of(S, "sweep.bwd_blocked")
+    levels = [(CHUNKED, int(lp[l]), int(lp[l + 1] - lp[l]), int(cp[l]), int(cp[l + 1] - cp[l])) if S.chunked_level(l)
+              else (PLAIN, int(lp[l]), int(lp[l + 1] - lp[l]), 0, 0) for l in range(S.nlevels)]
+    assert S.ntb >= 2
+    blocks = [(TAIL_BLOCK, 0, 0, kb, 0) for kb in range(S.ntb)]
+    assert fwd == levels + [(TAIL_GATHER, 0, 0, 0, 0)] + blocks
+    assert bwd == [(TAIL_DSCALE, 0, 0, 0, 0)] + blocks[::-1] + levels[::-1]
+    assert not any(st[0] in (SYNC_FREE, PRE) for st in fwd + bwd)
+
+
 def chunked_levels_in_range(S):
     return sum(bool(S.chunked_level(l)) for l in range(S.sf_level, S.nlevels))
 
@@ -377,6 +485,7 @@ def test_schedule(name, cus, monkeypatch):
     nsplit = check_gather(S)
     check_structure(S)
     check_tail_lists(S, cus)
+    check_sweep_steps(S)
     assert CASES[name](S, nsplit), (name, S.sf_level, chunked_levels_in_range(S), S.ntb, nsplit)
 
 
@@ -391,6 +500,62 @@ def test_schedule_with_visits(name, monkeypatch):
     assert check_visits(S) >= 1, "a visit"
     check_gather(S)
     check_structure(S)
+    check_sweep_steps(S)
+    # k_fwd_pre is counted where it runs; the commit before the lists launched it uncounted
+    pf, pb = PARENT_LAUNCHES_VISITS[name]
+    assert list(S["work.launches"]) == [pf + (1 if len(S["sf.pre_col"]) else 0), pb]
+
+
+# work.launches (forward, backward) of the commit before the step lists, whose
+# count_work restated the launch rule as arithmetic: recorded from a build of
+# that commit, not from the code under test.  The lists must total the same.
+PARENT_LAUNCHES = {
+    "default": ({}, {"afiro": (1, 1), "25fv47": (4, 3), "pds-02": (8, 7), "dfl001": (10, 9), "ken-07": (5, 5)}),
+    "merge0": ({"IPO_HIP_MERGE_LEVELS": "0"},
+               {"afiro": (1, 1), "25fv47": (4, 3), "pds-02": (12, 11), "dfl001": (16, 15), "ken-07": (8, 8)}),
+    "small1": ({"IPO_HIP_SMALL_LEAVES": "1"},
+               {"afiro": (1, 1), "25fv47": (5, 4), "pds-02": (13, 12), "dfl001": (16, 15), "ken-07": (8, 8)}),
+    "sf0": ({"IPO_HIP_SF": "0"},
+            {"afiro": (7, 7), "25fv47": (24, 23), "pds-02": (26, 25), "dfl001": (35, 34), "ken-07": (17, 17)}),
+}
+# the same with IPO_HIP_VISITS=1 (that commit did not count k_fwd_pre)
+PARENT_LAUNCHES_VISITS = {"25fv47": (4, 3), "pds-02": (8, 7)}
+
+
+@pytest.mark.parametrize("setting", list(PARENT_LAUNCHES))
+@pytest.mark.parametrize("name", list(CASES))
+def test_sweep_steps_total_the_parents_launches(name, setting, monkeypatch):
+    env, want = PARENT_LAUNCHES[setting]
+    S = load_env(name, 256, env, monkeypatch)
+    check_structure(S)
+    check_sweep_steps(S, merge=setting != "merge0")
+    assert tuple(int(x) for x in S["work.launches"]) == want[name]
+    kinds = {st[0] for st in steps_of(S, "sweep.fwd")}
+    assert setting != "sf0" or (SYNC_FREE not in kinds and S.sf_level == S.nlevels)
+
+
+def test_sweep_steps_see_every_level_kind(monkeypatch):
+    """between them the settings above reach every level kind (so the rule's branches are all checked)"""
+    seen = set()
+    for setting, name in (("sf0", "dfl001"), ("merge0", "pds-02"), ("small1", "pds-02")):
+        S = load_env(name, 256, PARENT_LAUNCHES[setting][0], monkeypatch)
+        seen |= {st[0] for st in steps_of(S, "sweep.fwd")}
+    assert seen >= set(LEVEL_KINDS), seen
+
+
+@pytest.mark.parametrize("env,pairs,lead", [({"IPO_HIP_CHAIN_PAIRS": "1"}, True, 1),
+                                            ({"IPO_HIP_CHAIN_LEAD": "0"}, False, 0)])
+def test_sweep_steps_tail_knobs(env, pairs, lead, monkeypatch):
+    S = load_env("25fv47", 256, env, monkeypatch)
+    assert S.nt > 0 and S.chain_lead == lead
+    check_sweep_steps(S, pairs=pairs)
+
+
+@pytest.mark.parametrize("name", ["dfl001", "25fv47"])
+def test_sweep_steps_blocked(name, monkeypatch):
+    """No committed problem has a tail of more than kChainMaxBlocks block columns: the builder's rule for one,
+    forced on here"""
+    check_blocked_steps(load_env(name, 256, {}, monkeypatch))
 
 
 def test_unknown_array_is_an_error():
