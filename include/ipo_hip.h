@@ -329,7 +329,8 @@ int ipo_hip_tail_run_schedule(int nt, int K, int L, int cap, unsigned *items, in
  * (nforced: trailing linking rows), the runtime knobs from the environment,
  * a device of `cus` compute units (kkt_schedule.h build_kkt_schedule).
  * name: "<part>.<member>" of KktSchedule ("sf.items_f", "gather.ck_u", ...),
- * "paths", "<part>.dims", or "plan.<member>" for the plan's own arrays;
+ * "paths", "<part>.dims", "sweep.split" (one entry: SweepSteps::split), or
+ * "plan.<member>" for the plan's own arrays;
  * pairs and triples come out flattened.  Several names separated by commas
  * give, for each in turn, its length followed by its entries (one build of
  * the plan for a whole schedule).  Returns the length of what the name asks

@@ -866,6 +866,7 @@ std::vector<int> schedule_array(const ipo::KktPlan& P, const ipo::KktKnobs& knob
     };
     if (name == "sweep.fwd") return steps(S.sweep.fwd);
     if (name == "sweep.bwd") return steps(S.sweep.bwd);
+    if (name == "sweep.split") return {S.sweep.split};
     if (name == "sweep.fwd_blocked" || name == "sweep.bwd_blocked") {
         const ipo::SweepSteps b = ipo::build_sweep_steps(P, knobs, S.paths, S.chunks, S.order, S.sf, true);
         return steps(name == "sweep.fwd_blocked" ? b.fwd : b.bwd);

@@ -608,8 +608,17 @@ int IpmSolver::run_hsd(const IpmOptions& opt, IpmResult* res) {
             // host-side effects are undone and an error it raised is held
             // back unless the iteration goes on to use the factor
             spec = K.host_state();
+            // the solves' right-hand sides are final at ev_side_: the factor
+            // runs their forward sparse sweep on the side stream beside its
+            // dense tail (KktDevice::PrePass), and solve2 below picks it up
+            KktDevice::PrePass pre;
+            pre.R = 2;
+            pre.dfy[0] = fy_.get(); pre.dfx[0] = fx_.get();
+            pre.dfy[1] = gy_.get(); pre.dfx[1] = gx_.get();
+            pre.stream = side_;
+            pre.ready = ev_side_;
             try {
-                K.factor(E_.get(), D_.get());
+                K.factor(E_.get(), D_.get(), &pre);
             } catch (...) {
                 spec_err = std::current_exception();
             }

@@ -10,6 +10,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <memory>
 #include <vector>
@@ -138,8 +139,27 @@ class KktDevice {
     // entries of out (m values) are not written
     void launch_q_long(const double* v, double* out);
 
+    // The forward pre-pass of the next solve's first refinement pass.  That
+    // pass's maxbc reduction, its k_perm_in2 and the forward steps [0,
+    // h_.sweep.split) (the sparse levels and k_tail_gather) read the sparse
+    // panels and the right-hand sides only, both final before the dense tail
+    // is factored: given a request, factor() enqueues them on the caller's
+    // side stream beside the tail's gather and k_tail_run, ordered by stream
+    // events alone, and solve_multi() called next with the same R and vectors
+    // starts its first sweep at the tail lead.  The kernels, their arguments
+    // and their order are the sequential pass's (bitwise).  Used only when the
+    // factorisation's first pass stood with no dependent pivot (the pre-pass
+    // ran with eps = 0, ldlt.c:446); otherwise, and at the next factor() or
+    // restore_host_state(), it is dropped: the normal pass rewrites all it wrote.
+    struct PrePass {
+        int R = 0;                        // 1 or 2 right-hand sides
+        double* dfy[2] = {nullptr, nullptr};
+        double* dfx[2] = {nullptr, nullptr};
+        hipStream_t stream = nullptr;     // the side stream (not the object's)
+        hipEvent_t ready = nullptr;       // recorded once dfy / dfx hold the right-hand sides
+    };
     // Numeric factorisation of K(E, D); E (m), D (n) are device vectors.
-    void factor(const double* dE, const double* dD);
+    void factor(const double* dE, const double* dD, const PrePass* pre = nullptr);
     // In-place refined solve of  -E dy + A dx = fy,  A' dy + D dx = fx.
     // Returns the rawsolve consistency flag of the last pass (1 = consistent).
     int solve(const double* dE, const double* dD, double* dfy, double* dfx);
@@ -149,7 +169,8 @@ class KktDevice {
     void solve_multi(int R, const double* dE, const double* dD, double* const* dfy, double* const* dfx, int* ok);
 
     // One unrefined sweep L D L' z = rhs on R permuted device vectors at dz + r K.
-    void rawsolve(double* dz, int R = 1);
+    // (fwd_first: the forward list from that step on, the steps before it done already)
+    void rawsolve(double* dz, int R = 1, size_t fwd_first = 0);
 
     // What a factorisation changes on the host side (eps_diag growth,
     // dependent-pivot count, timers and counters): saved before a
@@ -161,7 +182,7 @@ class KktDevice {
         KktTimers tm;
     };
     HostState host_state() const { return {epsdiag_, ndep_, tm_}; }
-    void restore_host_state(const HostState& h) { epsdiag_ = h.epsdiag; ndep_ = h.ndep; tm_ = h.tm; }
+    void restore_host_state(const HostState& h) { epsdiag_ = h.epsdiag; ndep_ = h.ndep; tm_ = h.tm; drop_prepass(); }
 
     double epsdiag() const { return epsdiag_; }
     void set_pivot_tolerance(double t) { pivot_tol_ = t; }   // (starts at IPO_HIP_PIVTOL, kkt_knobs.h)
@@ -209,15 +230,16 @@ class KktDevice {
     // the host repair backs the look-ahead panel's dependent pivots (TailView::dep):
     // not without the fused kernels, not in a sharded solve
     bool tail_repair() const { return use_panel_ && !xch_ && knobs_.tail_repair; }
-    void factor_core(const double* dE, const double* dD);
+    void factor_core(const double* dE, const double* dD, const PrePass* pre);
     void dump_factor(const double* dE, const double* dD, double eps_in);
     int dump_count_ = 0;
     TailView tail_view() const;
     template <int R>
-    void sweep(double* dz, const double* epsp);   // rawsolve's sweeps, sf_tbase, tail_rhs_*: kkt_sweep.hip
+    void sweep(double* dz, const double* epsp, size_t fwd_first);   // rawsolve's sweeps, sf_tbase, tail_rhs_*: kkt_sweep.hip
     // launches one list of h_.sweep in order; returns the kernels it launched
     template <int R>
-    int run_sweep_steps(const std::vector<SweepStep>& steps, bool forward, double* dz, const double* epsp);
+    int run_sweep_steps(const std::vector<SweepStep>& steps, bool forward, double* dz, const double* epsp,
+                        size_t first = 0, size_t last = SIZE_MAX, hipStream_t s = nullptr);   // steps [first, last) on s (null: stream_)
     void tail_rhs_begin(double* dz, int R);
     void tail_rhs_end(double* dz, int R);
     DevBuf<int> dIncons_;          // per right-hand side: inconsistent-system flag
@@ -290,7 +312,7 @@ class KktDevice {
 #ifdef IPO_SF_STAMPS
     std::vector<SchedInt2> h_sf_items_f_;    // forward sync-free items (host copy, developer stamps)
 #endif
-    int sf_tbase(int d, int nitems);
+    int sf_tbase(int d, int nitems, hipStream_t s);
     DevBuf<int2> dsf_items_f_, dsf_items_b_;
     DevBuf<int> dsf_need_, dsf_par_, dsf_zbase_, dsf_zpi_, dsf_fcnt_, dsf_fflag_, dsf_bcnt_, dsf_bflag_, dsf_ticket_;
     DevBuf<int> dybase_;                  // per supernode: first ybuf slot of its update values
@@ -298,8 +320,21 @@ class KktDevice {
     DevBuf<int> dfu_sup_, dfu_j_;         // fused panel unit -> supernode, tile pair index (per level: h_.fu_ptr)
     DevBuf<int> dsmall_sups_;             // small panels (per level: h_.small_ptr)
     const bool use_panel_ = knobs_.panel; // fused diagonal-block + panel kernels
-    bool factor_pass(const double* dE, const double* dD, bool fused, bool tail_fused);
-    void enqueue_levels(const PlanView& pv, const TailView& tv, bool fused, hipStream_t s);
+    bool factor_pass(const double* dE, const double* dD, bool fused, bool tail_fused, const PrePass* pre = nullptr);
+    // the forward pre-pass (PrePass above; IPO_HIP_PREPASS, kkt_knobs.h)
+    bool prepass_eligible(const PrePass* pre, bool fused, bool tail_fused) const;
+    void enqueue_prepass(const PrePass& pre);   // the fork after the sparse levels; records ev_pre_done_
+    void run_prepass_steps(int R, hipStream_t q);   // (kkt_sweep.hip)
+    void enqueue_pass_head(int R, double* const* dfy, double* const* dfx, double* part, hipStream_t s);
+    bool take_prepass(int R, double* const* dfy, double* const* dfx);
+    void drop_prepass() { if (pre_state_ != kPreNone) { pre_state_ = kPreNone; pre_discarded_++; } }
+    enum { kPreNone = 0, kPreEnqueued, kPreValid };
+    int pre_state_ = kPreNone;     // Enqueued: inside factor_core, its verdict pending; Valid: the next solve may use it
+    PrePass pre_req_;              // the request the enqueued pre-pass ran with
+    hipEvent_t ev_pre_fork_ = nullptr, ev_pre_done_ = nullptr;
+    long pre_used_ = 0, pre_discarded_ = 0;    // (IPO_HIP_DEBUG_REDO)
+    DevBuf<double> dPrePart_;      // the pre-pass's maxbc partials (dPart_ is finish_pass's meanwhile)
+    void enqueue_levels(const PlanView& pv, const TailView& tv, bool fused, hipStream_t s, const PrePass* pre);
     bool finish_pass(bool fused);
     void repair_tail();
     DevBuf<int> dsweep_sups_;             // level_sups in sweep order (leaves first on unchunked levels)
@@ -342,6 +377,10 @@ class KktDevice {
     DevBuf<int> dFlags_;           // [0] ndep, [1] fused bail bits, [2] 1 + bailed tail block, [4..] node sign
     DevBuf<double> dZ_, dDy_, dDx_, dRy_, dRx_;
     DevBuf<double> dPart_, dScal_;
+    // finish_pass's read-back (min|d| and the packed flags) has slots of its
+    // own: the pre-pass's k_perm_in2 zeroes dScal_[4..5] and its maxbc stands
+    // in dScal_[8..] while finish_pass runs
+    DevBuf<double> dFacScal_;
     double* hScal_ = nullptr;      // pinned
     int* hFlags_ = nullptr;        // pinned
 };

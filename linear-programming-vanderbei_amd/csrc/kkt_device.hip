@@ -1157,12 +1157,16 @@ void KktDevice::alloc_numeric() {
     dIncons_.alloc(2);
     dPart_.alloc(8 * kRedBlocks);
     dScal_.alloc(16);
+    dFacScal_.alloc(8);
+    dPrePart_.alloc(8 * kRedBlocks);
     IPO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hScal_), 16 * sizeof(double), hipHostMallocDefault));
     IPO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hFlags_), 8 * sizeof(int), hipHostMallocDefault));
     IPO_HIP_CHECK(hipEventCreate(&ev0_));
     IPO_HIP_CHECK(hipEventCreate(&ev1_));
     IPO_HIP_CHECK(hipEventCreate(&ev2_));
     IPO_HIP_CHECK(hipEventCreate(&ev3_));
+    IPO_HIP_CHECK(hipEventCreateWithFlags(&ev_pre_fork_, hipEventDisableTiming));
+    IPO_HIP_CHECK(hipEventCreateWithFlags(&ev_pre_done_, hipEventDisableTiming));
     IPO_HIP_CHECK(hipStreamSynchronize(s));
 }
 
@@ -1223,12 +1227,16 @@ KktDevice::~KktDevice() {
                              "k_panel_s %ld; tail block columns repaired %ld in %ld rounds\n", tm_.factors,
                      tm_.panel_redos, tm_.redo_where[0], tm_.redo_where[1], tm_.redo_where[2], tm_.redo_where[3],
                      tm_.tail_repairs, tm_.tail_dep_rounds);
+    if (knobs_.debug_redo)
+        std::fprintf(stderr, "kkt: forward pre-passes used %ld, discarded %ld\n", pre_used_, pre_discarded_);
     if (hScal_) (void)hipHostFree(hScal_);
     if (hFlags_) (void)hipHostFree(hFlags_);
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
     if (ev2_) (void)hipEventDestroy(ev2_);
     if (ev3_) (void)hipEventDestroy(ev3_);
+    if (ev_pre_fork_) (void)hipEventDestroy(ev_pre_fork_);
+    if (ev_pre_done_) (void)hipEventDestroy(ev_pre_done_);
     for (hipEvent_t e : kev_) (void)hipEventDestroy(e);
 }
 
@@ -1308,13 +1316,22 @@ void KktDevice::dump_factor(const double* dE, const double* dD, double eps_in) {
     std::fclose(f);
 }
 
-void KktDevice::factor(const double* dE, const double* dD) {
+void KktDevice::factor(const double* dE, const double* dD, const PrePass* pre) {
     const double eps_in = epsdiag_;
-    factor_core(dE, dD);
+    drop_prepass();               // one whose factor no solve followed
+    try {
+        factor_core(dE, dD, pre);
+    } catch (...) {
+        // an enqueued pre-pass is not used, and what follows on the object's
+        // stream comes after it (its done event is recorded already)
+        if (pre_state_ != kPreNone) (void)hipStreamWaitEvent(stream_, ev_pre_done_, 0);
+        drop_prepass();
+        throw;
+    }
     dump_factor(dE, dD, eps_in);
 }
 
-void KktDevice::factor_core(const double* dE, const double* dD) {
+void KktDevice::factor_core(const double* dE, const double* dD, const PrePass* pre) {
     // fast path: fused diagonal-block + panel kernels; a pivot that fails
     // the zero test makes them stop unwritten.  A bail in the dense tail
     // only: the look-ahead resumes from the bailed block column (repair);
@@ -1323,7 +1340,7 @@ void KktDevice::factor_core(const double* dE, const double* dD) {
     // by the look-ahead (its own bails repaired the same way) -- a per-phase
     // tail costs a single-workgroup partial substitution per block column
     const bool repair = tail_repair();
-    bool ok = factor_pass(dE, dD, use_panel_, use_panel_);
+    const bool ok = factor_pass(dE, dD, use_panel_, use_panel_, pre);
     if (!ok) {
         tm_.panel_redos++;
         for (int b = 0; b < 4; b++) tm_.redo_where[b] += (hFlags_[1] >> b) & 1;
@@ -1339,6 +1356,13 @@ void KktDevice::factor_core(const double* dE, const double* dD) {
     if (timing_)
         for (int ph : {kPhGather, kPhDiag, kPhTrsm, kPhSyrk, kPhTail}) tm_.phase_count[ph]++;
     ndep_ = xch_ ? static_cast<int>(hScal_[1]) : hFlags_[0];
+    // the pre-pass stands if the first pass did (no redo, no repair) and no
+    // pivot was dropped: it ran with eps = 0, which only a factor without
+    // dropped columns never reads (rawsolve, ldlt.c:446)
+    if (pre_state_ == kPreEnqueued) {
+        if (ok && ndep_ == 0) pre_state_ = kPreValid;
+        else drop_prepass();
+    }
     if (-hScal_[0] < 1.0e-14) epsdiag_ *= 10;
     // developer diagnostics (IPO_HIP_EPSDIAG_MAX, tools/status_loss_probe.py):
     // a cap on the growth above, to measure what a stalled solve owes to it
@@ -1349,7 +1373,7 @@ void KktDevice::factor_core(const double* dE, const double* dD) {
 // or the per-phase ones, the dense tail by the look-ahead (tail_fused) or
 // the per-phase kernels; returns false when fused kernels bailed out
 // (flags[1] says where; nothing of a bailed part may then be used).
-bool KktDevice::factor_pass(const double* dE, const double* dD, bool fused, bool tail_fused) {
+bool KktDevice::factor_pass(const double* dE, const double* dD, bool fused, bool tail_fused, const PrePass* pre) {
     hipStream_t s = stream_;
     if (timing_) IPO_HIP_CHECK(hipEventRecord(ev0_, s));
     const PlanView pv = plan_view();
@@ -1371,7 +1395,8 @@ bool KktDevice::factor_pass(const double* dE, const double* dD, bool fused, bool
                        dFlags_.get(), dkQ_.get() ? dQdiag_.get() : static_cast<const double*>(nullptr),
                        static_cast<double>(qmax_));
     const TailView tv = tail_view();
-    enqueue_levels(pv, tv, fused, s);
+    if (!prepass_eligible(pre, fused, tail_fused)) pre = nullptr;
+    enqueue_levels(pv, tv, fused, s, pre);
     if (plan_.nt > 0) {
         // shards: S = sum of every shard's assembled + gathered tail (exchange.h)
         xsum(tv.S, static_cast<size_t>(plan_.nt) * plan_.nt, RedOp::Sum);
@@ -1407,12 +1432,65 @@ bool KktDevice::factor_pass(const double* dE, const double* dD, bool fused, bool
             }
         }
     }
+    // The pre-pass joins the object's stream here, behind the tail's factor
+    // (ten times its length on dfl001): finish_pass's synchronisation then
+    // covers it, so whatever follows a factorisation on either stream -- a
+    // redo, a repair, a solve that does not use it, the next factorisation,
+    // an exception's unwinding -- finds its buffers at rest.
+    if (pre) IPO_HIP_CHECK(hipStreamWaitEvent(s, ev_pre_done_, 0));
     return finish_pass(fused || tail_fused);
+}
+
+// Whether this pass of the factorisation takes the caller's pre-pass request:
+// the first pass only (factor_core passes the request to no other), fused
+// panels and the persistent tail, a forward list with a TailGather / TailLead
+// pair, one GPU, no timing mode (its phase events would time two streams).
+bool KktDevice::prepass_eligible(const PrePass* pre, bool fused, bool tail_fused) const {
+    return knobs_.prepass && pre && (pre->R == 1 || pre->R == 2) && pre->stream && pre->stream != stream_ &&
+           pre->ready && fused && tail_fused && h_.paths.tail_run && h_.sweep.split > 0 && !xch_ && !timing_;
+}
+
+// The head of a solve's first refinement pass for R right-hand sides, on s:
+// maxbc_r = MAX(maxv(fx_r), maxv(fy_r)) + 1 (ldlt.c:367) into dScal_[8 ..],
+// read back with the pass's residuals (no copy or wait of its own), and the
+// right-hand sides permuted into dZ_ (k_perm_in2, which also clears the
+// sweep's eps slots and consistency flags).  part: the reduction's partials.
+void KktDevice::enqueue_pass_head(int R, double* const* dfy, double* const* dfx, double* part, hipStream_t s) {
+    RedJobs j{};
+    j.nj = 2 * R;
+    PermJobs J{};
+    for (int r = 0; r < R; r++) {
+        j.a[2 * r] = dfx[r]; j.b[2 * r] = nullptr; j.len[2 * r] = n_; j.op[2 * r] = 1;
+        j.a[2 * r + 1] = dfy[r]; j.b[2 * r + 1] = nullptr; j.len[2 * r + 1] = m_; j.op[2 * r + 1] = 1;
+        J.fy[r] = dfy[r];
+        J.fx[r] = dfx[r];
+        J.z[r] = dZ_.get() + static_cast<size_t>(r) * T_;
+    }
+    launch_reduce(j, part, dScal_.get() + 8, s);
+    xsum(dScal_.get() + 8, 2 * R, RedOp::Max);
+    hipLaunchKernelGGL(k_perm_in2, dim3(ceil_div(T_, NT), R), dim3(NT), 0, s, T_, m_, dperm_.get(), J, dIncons_.get(),
+                       dScal_.get() + 4);
+}
+
+// The forward pre-pass (kkt_device.h PrePass), forked off the object's stream
+// where it stands: behind the last sparse panel.  What it touches, against
+// what the object's stream runs meanwhile (the tail's gather, k_tail_run,
+// finish_pass after the join): DESIGN.md 6.5.
+void KktDevice::enqueue_prepass(const PrePass& pre) {
+    hipStream_t q = pre.stream;
+    IPO_HIP_CHECK(hipEventRecord(ev_pre_fork_, stream_));
+    IPO_HIP_CHECK(hipStreamWaitEvent(q, ev_pre_fork_, 0));
+    IPO_HIP_CHECK(hipStreamWaitEvent(q, pre.ready, 0));
+    enqueue_pass_head(pre.R, pre.dfy, pre.dfx, dPrePart_.get(), q);
+    run_prepass_steps(pre.R, q);
+    IPO_HIP_CHECK(hipEventRecord(ev_pre_done_, q));
+    pre_req_ = pre;
+    pre_state_ = kPreEnqueued;
 }
 
 // The sparse levels (gather, then panels, level by level) and the dense
 // tail's gather of one factorisation, enqueued on s.
-void KktDevice::enqueue_levels(const PlanView& pv, const TailView& tv, bool fused, hipStream_t s) {
+void KktDevice::enqueue_levels(const PlanView& pv, const TailView& tv, bool fused, hipStream_t s, const PrePass* pre) {
     for (int l = 0; l < plan_.nlevels; l++) {
         const int u0 = plan_.unit_level_ptr[l], u1 = plan_.unit_level_ptr[l + 1];
         if (u1 <= u0) continue;
@@ -1448,6 +1526,7 @@ void KktDevice::enqueue_levels(const PlanView& pv, const TailView& tv, bool fuse
             ph_end(kPhTrsm, 1, s);
         }
     }
+    if (pre) enqueue_prepass(*pre);       // the sparse panels are final from here on
     if (plan_.nt > 0) {
         ph_begin(s);
         const int nl = launch_gather(pv, tv, 0, plan_.nlevels, s);
@@ -1462,17 +1541,17 @@ bool KktDevice::finish_pass(bool fused) {
     IPO_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_min_abs_partial, dim3(kRedBlocks), dim3(NT), 0, s, dDg_.get(), T_, dPart_.get());
     if (xch_) {   // every shard must take the same eps_diag / dependent-pivot / redo decisions
-        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, dPart_.get(), 1, 1u, dScal_.get());
-        hipLaunchKernelGGL(k_flag_to_scalar, dim3(1), dim3(1), 0, s, dFlags_.get(), dScal_.get() + 1);
-        hipLaunchKernelGGL(k_flag_to_scalar, dim3(1), dim3(1), 0, s, dFlags_.get() + 1, dScal_.get() + 2);
-        xsum(dScal_.get(), 3, RedOp::Max);
-        hipLaunchKernelGGL(k_pack_ints, dim3(1), dim3(3), 0, s, dFlags_.get(), 3, dScal_.get() + 3);
+        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, dPart_.get(), 1, 1u, dFacScal_.get());
+        hipLaunchKernelGGL(k_flag_to_scalar, dim3(1), dim3(1), 0, s, dFlags_.get(), dFacScal_.get() + 1);
+        hipLaunchKernelGGL(k_flag_to_scalar, dim3(1), dim3(1), 0, s, dFlags_.get() + 1, dFacScal_.get() + 2);
+        xsum(dFacScal_.get(), 3, RedOp::Max);
+        hipLaunchKernelGGL(k_pack_ints, dim3(1), dim3(3), 0, s, dFlags_.get(), 3, dFacScal_.get() + 3);
     } else {
         // min|d| and the three flags in one read-back, one launch
-        hipLaunchKernelGGL(k_finish_reduce_pack, dim3(1), dim3(kRedThreads), 0, s, dPart_.get(), 1, 1u, dScal_.get(),
-                           static_cast<const int*>(dFlags_.get()), 3, dScal_.get() + 3);
+        hipLaunchKernelGGL(k_finish_reduce_pack, dim3(1), dim3(kRedThreads), 0, s, dPart_.get(), 1, 1u, dFacScal_.get(),
+                           static_cast<const int*>(dFlags_.get()), 3, dFacScal_.get() + 3);
     }
-    IPO_HIP_CHECK(hipMemcpyAsync(hScal_, dScal_.get(), 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+    IPO_HIP_CHECK(hipMemcpyAsync(hScal_, dFacScal_.get(), 5 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (timing_) IPO_HIP_CHECK(hipEventRecord(ev1_, s));
     IPO_HIP_CHECK(hipStreamSynchronize(s));
     if (gst_n_ > 0) {      // developer stamps of one gather launch (IPO_HIP_GATHER_STAMPS)
@@ -1700,17 +1779,10 @@ void KktDevice::solve_multi(int R, const double* dE, const double* dD, double* c
     hipStream_t s = stream_;
     if (timing_) IPO_HIP_CHECK(hipEventRecord(ev0_, s));
     const int m = m_, n = n_, T = T_;
-    {   // maxbc_r = MAX(maxv(fx_r), maxv(fy_r)) + 1   (ldlt.c:367)
-        RedJobs j{};
-        j.nj = 2 * R;
-        for (int r = 0; r < R; r++) {
-            j.a[2 * r] = dfx[r]; j.b[2 * r] = nullptr; j.len[2 * r] = n; j.op[2 * r] = 1;
-            j.a[2 * r + 1] = dfy[r]; j.b[2 * r + 1] = nullptr; j.len[2 * r + 1] = m; j.op[2 * r + 1] = 1;
-        }
-        // read back with the first pass's residuals (no copy or wait of its own)
-        launch_reduce(j, dPart_.get(), dScal_.get() + 8, s);
-        xsum(dScal_.get() + 8, 2 * R, RedOp::Max);
-    }
+    // the first pass's head and the forward steps before the tail lead: done
+    // beside the factorisation (the pre-pass, joined there), or now
+    const bool pre = take_prepass(R, dfy, dfx);
+    if (!pre && R > 0) enqueue_pass_head(R, dfy, dfx, dPart_.get(), s);
     double maxbc[2] = {0.0, 0.0}, rs[2] = {HUGE_VAL, HUGE_VAL}, rs_old[2] = {HUGE_VAL, HUGE_VAL};
     int pass[2] = {0, 0};
     bool active[2] = {R > 0, R > 1};
@@ -1724,13 +1796,14 @@ void KktDevice::solve_multi(int R, const double* dE, const double* dD, double* c
     // right-hand-side slot q of an active system is read back after it
     int incons[2] = {0, 0};
     while (active[0] || active[1]) {
-        {
+        const bool first = pass[0] + pass[1] == 0;     // (every system is active in it)
+        if (!first) {
             PermJobs J{};
             int na = 0;
             for (int r = 0; r < R; r++)
                 if (active[r]) {
-                    J.fy[na] = pass[r] == 0 ? dfy[r] : ryv(r);
-                    J.fx[na] = pass[r] == 0 ? dfx[r] : rxv(r);
+                    J.fy[na] = ryv(r);
+                    J.fx[na] = rxv(r);
                     J.z[na] = zv(r);
                     na++;
                 }
@@ -1738,8 +1811,9 @@ void KktDevice::solve_multi(int R, const double* dE, const double* dD, double* c
                                dIncons_.get(), dScal_.get() + 4);
         }
         eps_cleared_ = true;
-        if (active[0] && active[1]) rawsolve(zv(0), 2);
-        else rawsolve(zv(active[0] ? 0 : 1), 1);
+        const size_t fwd_first = first && pre ? static_cast<size_t>(h_.sweep.split) : 0;
+        if (active[0] && active[1]) rawsolve(zv(0), 2, fwd_first);
+        else rawsolve(zv(active[0] ? 0 : 1), 1, fwd_first);
         eps_cleared_ = false;
         int nq = 0;
         {
@@ -1824,6 +1898,21 @@ void KktDevice::solve_multi(int R, const double* dE, const double* dD, double* c
     tm_.solves += R;
     last_passes_ = pass[0] + pass[1];
     for (int r = 0; r < R; r++) ok[r] = incons[r] ? 0 : 1;
+}
+
+// Whether the solve about to start finds its first pass's head and leading
+// forward steps done by the last factorisation's pre-pass: one that stood
+// (factor_core), for these right-hand sides.  Used or not, it is spent.
+bool KktDevice::take_prepass(int R, double* const* dfy, double* const* dfx) {
+    bool same = pre_state_ == kPreValid && !timing_ && pre_req_.R == R;
+    for (int r = 0; same && r < R; r++) same = pre_req_.dfy[r] == dfy[r] && pre_req_.dfx[r] == dfx[r];
+    if (!same) {
+        drop_prepass();
+        return false;
+    }
+    pre_state_ = kPreNone;
+    pre_used_++;
+    return true;
 }
 
 int KktDevice::solve(const double* dE, const double* dD, double* dfy, double* dfx) {

@@ -51,6 +51,19 @@ struct KktKnobs {
     // an Exchange); 0: the sequential iteration, bitwise.
     // test_gpu_panel.py::test_hsd_overlap_bitwise
     bool overlap = true;
+    // IPO_HIP_PREPASS (default 1; 0 off): the overlapped HSD iteration has the
+    // factorisation enqueue the first solve's maxbc, k_perm_in2 and forward
+    // steps up to k_tail_gather on the side stream beside the dense tail's
+    // factor (KktDevice::PrePass; fused panels, the persistent tail and the
+    // lead sweep only); 0: the solve runs them itself, bitwise.  No gate on
+    // the tail's block count: measured on one box, off against on alternated
+    // (dfl001, 70 block columns: 292.9 -> 299.1 it/s; the others HSD solve
+    // time in ms): greenbea (12) 252 -> 240; 25fv47 (7) 98.6 -> 90.7; nesm (6) 364 -> 352;
+    // fffff800 (5) 74.7 -> 70.1; bnl1 (4) 94.1 -> 88.5; maros (4) 582 -> 569;
+    // brandy (3) 26.4 -> 24.3; beaconfd (3) 20.3 -> 18.8; forplan, sctap3,
+    // grow15 within their spread -- no tail small enough to lose.
+    // test_gpu_prepass.py
+    bool prepass = true;
     // IPO_HIP_CHAIN_LEAD (default on unless it parses to 0; dense tails of at
     // most kChainMaxBlocks block columns): the forward dense-tail sweep by one
     // lead workgroup + helpers (k_tail_fwd_lead); 0: the per-block chain,
@@ -222,6 +235,7 @@ struct KktKnobs {
         k.merge_levels = flag("IPO_HIP_MERGE_LEVELS", true);
         k.sf = flag("IPO_HIP_SF", true);
         k.overlap = flag("IPO_HIP_OVERLAP", true);
+        k.prepass = flag("IPO_HIP_PREPASS", true);
         k.chain_lead = flag("IPO_HIP_CHAIN_LEAD", true);
         k.chain_pairs = flag("IPO_HIP_CHAIN_PAIRS", false);
         k.tail_run = flag("IPO_HIP_TAIL_RUN", true);

@@ -411,6 +411,12 @@ int sweep_launches(const std::vector<SweepStep>& steps) {
     return n;
 }
 
+int sweep_split(const std::vector<SweepStep>& fwd) {
+    for (size_t i = 0; i + 1 < fwd.size(); i++)
+        if (fwd[i].kind == kSwTailGather) return fwd[i + 1].kind == kSwTailLead ? static_cast<int>(i) + 1 : 0;
+    return 0;
+}
+
 SweepSteps build_sweep_steps(const KktPlan& P, const KktKnobs& knobs, const KktPaths& paths, const SolveChunks& ch,
                              const SweepOrder& order, const SyncFreePlan& sf, bool blocked) {
     SweepSteps r;
@@ -448,6 +454,7 @@ SweepSteps build_sweep_steps(const KktPlan& P, const KktKnobs& knobs, const KktP
     }
     if (range) r.bwd.push_back({kSwSyncFree, 0, static_cast<int>(sf.items_b.size()), 0, 0});
     for (int l = top - 1; l >= 0; l--) level(l, r.bwd);
+    r.split = sweep_split(r.fwd);
     return r;
 }
 

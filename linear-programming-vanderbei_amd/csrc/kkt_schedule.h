@@ -75,7 +75,17 @@ enum SweepKind {
     kSwTailDscale,    // k_tail_dscale (blocked tails)
 };
 struct SweepStep { int kind, q0, n, a, b; };
-struct SweepSteps { std::vector<SweepStep> fwd, bwd; };   // in launch order
+struct SweepSteps {
+    std::vector<SweepStep> fwd, bwd;   // in launch order
+    // Leading forward steps that read only the sparse panels and the
+    // right-hand side: fwd[0, split) ends with the list's TailGather, and
+    // fwd[split] is the TailLead.  KktDevice enqueues them beside the dense
+    // tail's factorisation (the forward pre-pass, kkt_device.h).  0: no such
+    // pair in the list (no tail, a blocked tail, the per-block chain).
+    int split = 0;
+};
+// the rule of SweepSteps::split, on any forward list
+int sweep_split(const std::vector<SweepStep>& fwd);
 // kernel launches of a list: Chunked two, every other step one
 int sweep_launches(const std::vector<SweepStep>& steps);
 

@@ -2168,11 +2168,11 @@ void KktDevice::dump_sf_stamps() const {
 // Substitution sweeps for R right-hand sides stored at dz + r * K: the two
 // step lists of the schedule (h_.sweep, kkt_schedule.h), walked in order.
 template <int R>
-void KktDevice::sweep(double* dz, const double* epsp) {
+void KktDevice::sweep(double* dz, const double* epsp, size_t fwd_first) {
     hipStream_t s = stream_;
     if (timing_) IPO_HIP_CHECK(hipEventRecord(ev2_, s));
     ph_begin(s);
-    const int nf = run_sweep_steps<R>(h_.sweep.fwd, true, dz, epsp);
+    const int nf = run_sweep_steps<R>(h_.sweep.fwd, true, dz, epsp, fwd_first);
     ph_end(kPhForward, nf, s);
     ph_begin(s);
     const int nb = run_sweep_steps<R>(h_.sweep.bwd, false, dz, epsp);
@@ -2199,17 +2199,22 @@ void KktDevice::sweep(double* dz, const double* epsp) {
 // emits the kernel instances in; k_fwd_level<1> and k_fwd_leaf<1> get their
 // address arithmetic scheduled differently unless k_forward<1> is emitted
 // before them, so Plain stays ahead of the leaf kinds (device code compared
-// across changes stays identical).
+// across changes stays identical).  Steps [first, last) of the list (last
+// clipped to its end), on stream s (null: the object's): the forward
+// pre-pass runs the head of the forward list on the caller's side stream, and
+// the solve that uses it the rest (kkt_device.h PrePass).
 template <int R>
-int KktDevice::run_sweep_steps(const std::vector<SweepStep>& steps, bool forward, double* dz, const double* epsp) {
-    hipStream_t s = stream_;
+int KktDevice::run_sweep_steps(const std::vector<SweepStep>& steps, bool forward, double* dz, const double* epsp,
+                               size_t first, size_t last, hipStream_t s) {
+    if (!s) s = stream_;
     const PlanView pv = plan_view();
     const TailView tv = tail_view();
     const SweepVecs V{dz, static_cast<size_t>(T_), dYbuf_.get(), h_.ybuf_stride};
     const size_t ps = h_.partial_stride;
     const int nt = plan_.nt;
     int launched = 0;
-    for (const SweepStep& step : steps) {
+    for (size_t i = first; i < std::min(last, steps.size()); i++) {
+        const SweepStep& step = steps[i];
         const int q0 = step.q0, n = step.n;
         switch (step.kind) {
         case kSwChunked: {
@@ -2269,7 +2274,7 @@ int KktDevice::run_sweep_steps(const std::vector<SweepStep>& steps, bool forward
             if (forward) {
                 const SfView sf{dsf_items_f_.get(), n, dsf_fcnt_.get(), dsf_fflag_.get(), dsf_need_.get(),
                                 dsf_par_.get(), dsf_zbase_.get(), dsf_zpi_.get(), dZpad_.get(), h_.zpad_stride,
-                                ++sf_fwd_epoch_, dsf_ticket_.get(), sf_tbase(0, n)};
+                                ++sf_fwd_epoch_, dsf_ticket_.get(), sf_tbase(0, n, s)};
                 const bool pre = step.a != 0;
                 hipLaunchKernelGGL(k_fwd_sf<R>, dim3(std::min(sf_grid_, n)), dim3(NT), kChainLds, s, pv, sf,
                                    pre ? dylate_ptr_.get() : dyrow_ptr_.get(),
@@ -2277,7 +2282,7 @@ int KktDevice::run_sweep_steps(const std::vector<SweepStep>& steps, bool forward
             } else {
                 const SfView sf{dsf_items_b_.get(), n, dsf_bcnt_.get(), dsf_bflag_.get(), dsf_need_.get(),
                                 dsf_par_.get(), dsf_zbase_.get(), dsf_zpi_.get(), dZpad_.get(), h_.zpad_stride,
-                                ++sf_bwd_epoch_, dsf_ticket_.get() + 1, sf_tbase(1, n)};
+                                ++sf_bwd_epoch_, dsf_ticket_.get() + 1, sf_tbase(1, n, s)};
                 hipLaunchKernelGGL(k_bwd_sf<R>, dim3(std::min(sf_grid_, n)), dim3(NT), kChainLds, s, pv, sf,
                                    dchunk_r0_.get(), dsup_chunk0_.get(), dPartial_.get(), ps, V, epsp);
             }
@@ -2349,13 +2354,22 @@ int KktDevice::run_sweep_steps(const std::vector<SweepStep>& steps, bool forward
     return launched;
 }
 
+// The forward pre-pass's share of the forward list (kkt_device.h PrePass):
+// steps [0, split) for the R right-hand sides in dZ_, on q.
+void KktDevice::run_prepass_steps(int R, hipStream_t q) {
+    double* epsp = dScal_.get() + 4;
+    const size_t split = static_cast<size_t>(h_.sweep.split);
+    if (R == 2) run_sweep_steps<2>(h_.sweep.fwd, true, dZ_.get(), epsp, 0, split, q);
+    else run_sweep_steps<1>(h_.sweep.fwd, true, dZ_.get(), epsp, 0, split, q);
+}
+
 // Ticket base of the next sync-free launch of direction d over nitems items:
 // each launch draws nitems + grid tickets; the counter is cleared (in stream
 // order) before it could overflow.
-int KktDevice::sf_tbase(int d, int nitems) {
+int KktDevice::sf_tbase(int d, int nitems, hipStream_t s) {
     const long long draw = static_cast<long long>(nitems) + std::min(sf_grid_, nitems);
     if (sf_ticket_next_[d] + draw > (1LL << 30)) {
-        IPO_HIP_CHECK(hipMemsetAsync(dsf_ticket_.get() + d, 0, sizeof(int), stream_));
+        IPO_HIP_CHECK(hipMemsetAsync(dsf_ticket_.get() + d, 0, sizeof(int), s));
         sf_ticket_next_[d] = 0;
     }
     const int base = static_cast<int>(sf_ticket_next_[d]);
@@ -2375,7 +2389,7 @@ void KktDevice::tail_rhs_end(double* dz, int R) {
 }
 
 // rawsolve (ldlt.c:433-505) of R right-hand sides at dz + r * K, in place.
-void KktDevice::rawsolve(double* dz, int R) {
+void KktDevice::rawsolve(double* dz, int R, size_t fwd_first) {
     hipStream_t s = stream_;
     double* epsp = dScal_.get() + 4;        // eps of right-hand side r at epsp[r]
     if (ndep_ > 0) {
@@ -2390,9 +2404,9 @@ void KktDevice::rawsolve(double* dz, int R) {
         IPO_HIP_CHECK(hipMemsetAsync(epsp, 0, R * sizeof(double), s));
     }
     if (R == 2 && !h_.paths.tail_blocked) {
-        sweep<2>(dz, epsp);
+        sweep<2>(dz, epsp, fwd_first);
     } else {                         // (a blocked tail's per-block kernels: one right-hand side at a time)
-        for (int r = 0; r < R; r++) sweep<1>(dz + (size_t)r * T_, epsp + r);
+        for (int r = 0; r < R; r++) sweep<1>(dz + (size_t)r * T_, epsp + r, fwd_first);
     }
     tm_.rawsolves += R;
 }
