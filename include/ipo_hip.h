@@ -323,13 +323,20 @@ int ipo_hip_synth_block_angular(int nblocks, int mb, int nb, int per_col, int ba
  * caller built for that argument list from binding to this one.) */
 int ipo_hip_tail_run_schedule(int nt, int K, int L, int cap, unsigned *items, int max_items, int *ptr);
 
+/* Per block column t of a dense tail of nt columns: the count of the run's
+ * "column readable" counter (TailRun::cdone) that the trailing forward lead
+ * waits for (kkt_schedule.h lead_col_target; host-only test entry, no
+ * reference counterpart).  Writes at most cap entries to out (may be NULL);
+ * returns the number of block columns, or -1 (ipo_hip_last_error). */
+int ipo_hip_lead_col_targets(int nt, int *out, int cap);
+
 /* One integer array of the launch schedule a KktFactor of this pattern builds
  * before it uploads anything (host-only; test entry, no reference
  * counterpart, no HIP call): the plan as ipo_hip_symbolic_tail builds it
  * (nforced: trailing linking rows), the runtime knobs from the environment,
  * a device of `cus` compute units (kkt_schedule.h build_kkt_schedule).
  * name: "<part>.<member>" of KktSchedule ("sf.items_f", "gather.ck_u", ...),
- * "paths", "<part>.dims", "sweep.split" (one entry: SweepSteps::split), or
+ * "paths", "<part>.dims", "sweep.split" / "sweep.lead_end" (one entry: SweepSteps::split, ::lead_end), or
  * "plan.<member>" for the plan's own arrays;
  * pairs and triples come out flattened.  Several names separated by commas
  * give, for each in turn, its length followed by its entries (one build of

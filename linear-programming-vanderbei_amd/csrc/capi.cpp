@@ -867,6 +867,7 @@ std::vector<int> schedule_array(const ipo::KktPlan& P, const ipo::KktKnobs& knob
     if (name == "sweep.fwd") return steps(S.sweep.fwd);
     if (name == "sweep.bwd") return steps(S.sweep.bwd);
     if (name == "sweep.split") return {S.sweep.split};
+    if (name == "sweep.lead_end") return {S.sweep.lead_end};
     if (name == "sweep.fwd_blocked" || name == "sweep.bwd_blocked") {
         const ipo::SweepSteps b = ipo::build_sweep_steps(P, knobs, S.paths, S.chunks, S.order, S.sf, true);
         return steps(name == "sweep.fwd_blocked" ? b.fwd : b.bwd);
@@ -925,6 +926,18 @@ int ipo_hip_tail_run_schedule(int nt, int K, int L, int cap, unsigned* items, in
             }
         if (ptr) std::copy(pv.begin(), pv.end(), ptr);
         return n;
+    } catch (const std::exception& e) {
+        set_err(e.what());
+        return -1;
+    }
+}
+
+int ipo_hip_lead_col_targets(int nt, int* out, int cap) {
+    try {
+        if (nt <= 0) throw std::invalid_argument("lead_col_targets: bad arguments");
+        const int ntb = (nt + ipo::kPanelCols - 1) / ipo::kPanelCols;
+        for (int t = 0; out && t < std::min(ntb, cap); t++) out[t] = ipo::lead_col_target(nt, t);
+        return ntb;
     } catch (const std::exception& e) {
         set_err(e.what());
         return -1;

@@ -797,7 +797,11 @@ struct NoWait {
 // post(bailed): called by every thread once the handed-off results are
 // stored (the tile rows and, workgroup 0, D) -- k_tail_run signals step t
 // there, before workgroup 0's L11' / mark / |terms| stores, which only later
-// launches read -- or with true when the panel bails
+// launches read -- or with true when the panel bails.  (One reader does not
+// wait for a later launch: a trailing forward lead, k_tail_fwd_lead<R, true>,
+// reads column t's tiles, L11' and marks while the run goes on.  k_tail_run
+// tells it with a counter of its own, TailRun::cdone, raised after the last
+// of these stores.)
 struct NoPost {
     __device__ void operator()(bool) const {}
 };
@@ -1243,7 +1247,13 @@ __device__ __forceinline__ bool panel_w_body(const PlanView& p, const int* __res
             if (c < nc) st_h<SC>(panel + row + (size_t)c * ld, a[q]);
         }
     }
-    if (j == 0 && tid < nc) { st_h<SC>(p.dg + c0 + tid, dv[tid]); p.live[c0 + tid] = DEP ? S.lv[tid] != 0 : 1; }
+    if (j == 0 && tid < nc) {
+        st_h<SC>(p.dg + c0 + tid, dv[tid]);
+        // (SC: a trailing forward lead reads the marks while the run goes on, TailRun::cdone)
+        const int lvk = DEP ? S.lv[tid] != 0 : 1;
+        if constexpr (SC) __hip_atomic_store(p.live + c0 + tid, lvk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else p.live[c0 + tid] = lvk;
+    }
     post(false);
     if (!fu_sup && pre && j == 0 && !h1 && lane < nc && (lane >> 4) == w) st_h<SC>(p.dscale + c0 + lane, dsc_pre);
     if (j != 0) return false;
@@ -1626,7 +1636,11 @@ k_tail_run(PlanView p, TailView tv, TailRun rc) {
             if (tr && threadIdx.x == 0) tr[1] = __builtin_amdgcn_s_memrealtime();
             return go;
         };
-        auto post = [&](bool bailed) { run_signal(rc.pdone + t, bailed ? 1 + kRunBail : 1); };
+        bool held = false;     // the panel stored its column (post(false) reached; workgroup-uniform)
+        auto post = [&](bool bailed) {
+            run_signal(rc.pdone + t, bailed ? 1 + kRunBail : 1);
+            held = !bailed;
+        };
         if (tr && threadIdx.x == 0 && t == 0) tr[1] = __builtin_amdgcn_s_memrealtime();
         PanelLds& S = *reinterpret_cast<PanelLds*>(lds);
         const RunPub rp{rc.pub, rc.wflag, rc.wflag, rc.pread, rc.t0, rc.epoch, vd, vt, q, &sh_ok};
@@ -1636,6 +1650,13 @@ k_tail_run(PlanView p, TailView tv, TailRun rc) {
             panel_w_body<true, true>(p, nullptr, nullptr, 0, tv, t, j, S, nullptr, t > 0, nullptr, t, tv.dep, NoWait{},
                                      post, rp);
         }
+        // column t readable by a trailing forward lead (TailRun::cdone): after
+        // this workgroup's last store of the step -- workgroup 0's L11', which
+        // follows post() -- and only if the panel held, so the count of step t
+        // reaches tail_gp(nt, t) exactly when the column is final (a DEP
+        // pass's column included: it posts once, at its own end).  Off the
+        // step's critical path: nothing in the run waits for it.
+        if (rc.cdone && held) run_signal(rc.cdone + t);
     } else {
         // visit: chunk q of tile (bi, c), once the panels of step t - 1 are done
         const int bi = rec.x & 255, c = (rec.x >> 8) & 255, b0 = (rec.x >> 16) & 255, b1 = rec.x >> 24;

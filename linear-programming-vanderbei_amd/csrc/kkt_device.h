@@ -53,6 +53,11 @@ struct TailRun {
     int* ticket;
     int* pdone;
     int* vseq;
+    // [ntb] (null: off) panel workgroups of step t that held and have stored
+    // everything of the step, workgroup 0's L11' included: tail_gp(nt, t) of
+    // them make block column t readable while the run goes on (the trailing
+    // forward lead, k_tail_fwd_lead<R, true>; never reached if a panel bails)
+    int* cdone = nullptr;
     // window hand-off (kkt_dense.hip RunPub; null: off): tile window (t, j, w)
     // at pub + (((t & 1) ntb + j) 4 + w) kTailPubWin once wflag[(t ntb + j) 4
     // + w] == epoch (one epoch per launch, never reused: no reset)
@@ -327,12 +332,29 @@ class KktDevice {
     void run_prepass_steps(int R, hipStream_t q);   // (kkt_sweep.hip)
     void enqueue_pass_head(int R, double* const* dfy, double* const* dfx, double* part, hipStream_t s);
     bool take_prepass(int R, double* const* dfy, double* const* dfx);
-    void drop_prepass() { if (pre_state_ != kPreNone) { pre_state_ = kPreNone; pre_discarded_++; } }
+    void drop_prepass() {
+        if (pre_state_ != kPreNone) { pre_state_ = kPreNone; pre_discarded_++; lead_discarded_ += pre_lead_; }
+        pre_lead_ = false;
+        lead_pending_ = 0;
+    }
     enum { kPreNone = 0, kPreEnqueued, kPreValid };
     int pre_state_ = kPreNone;     // Enqueued: inside factor_core, its verdict pending; Valid: the next solve may use it
     PrePass pre_req_;              // the request the enqueued pre-pass ran with
     hipEvent_t ev_pre_fork_ = nullptr, ev_pre_done_ = nullptr;
     long pre_used_ = 0, pre_discarded_ = 0;    // (IPO_HIP_DEBUG_REDO)
+    // The pre-pass extended by the forward tail lead in its trailing form
+    // (IPO_HIP_LEAD_TRAIL, kkt_knobs.h; k_tail_fwd_lead<R, true>, DESIGN.md
+    // 6.6): enqueue_prepass asks for it (lead_pending_: the mode),
+    // launch_tail_from(0, true) enqueues it after k_tail_run (pre_lead_), and
+    // it stands or is dropped with the pre-pass; the solve then starts its
+    // first sweep at h_.sweep.lead_end.
+    int lead_pending_ = 0;
+    bool pre_lead_ = false;
+    hipEvent_t ev_run_reset_ = nullptr;        // mode 2: the run's counters are reset
+    long lead_used_ = 0, lead_discarded_ = 0;  // (IPO_HIP_DEBUG_REDO)
+    void launch_lead_trail(int R, hipStream_t s, bool beside);   // (kkt_sweep.hip)
+    // TailRun::cdone, then the trailing lead's ticket: behind pread in drun_cnt_
+    int* run_cdone() { return drun_cnt_.get() + 1 + plan_.ntb + static_cast<size_t>(plan_.ntb) * plan_.ntb + plan_.ntb; }
     DevBuf<double> dPrePart_;      // the pre-pass's maxbc partials (dPart_ is finish_pass's meanwhile)
     void enqueue_levels(const PlanView& pv, const TailView& tv, bool fused, hipStream_t s, const PrePass* pre);
     bool finish_pass(bool fused);
@@ -359,7 +381,7 @@ class KktDevice {
     DevBuf<unsigned> dvisit_list_;     // TailView::vlist (tail_visit_schedule; knobs_.visit_sched off: none)
     // the dense tail as one persistent launch (k_tail_run; knobs_.tail_run off: one launch per step)
     DevBuf<uint2> drun_items_;         // tail_run_schedule (first item of each launch: h_.run_ptr)
-    DevBuf<int> drun_cnt_;             // ticket, pdone[ntb], vseq[ntb * ntb], pread[ntb]
+    DevBuf<int> drun_cnt_;             // ticket, pdone[ntb], vseq[ntb * ntb], pread[ntb], cdone[ntb], lead ticket
     // the run's window hand-off (TailRun::pub; knobs_.tail_winpub)
     DevBuf<double> drun_pub_;          // [2 * ntb * 4 * kTailPubWin]
     DevBuf<int> drun_wflag_;           // [ntb * ntb * 4], zeroed once

@@ -1119,7 +1119,8 @@ void KktDevice::setup_tail(int cus) {
             static_assert(sizeof(SchedUint2) == sizeof(uint2), "SchedUint2 is uploaded as uint2");
             drun_items_.upload(reinterpret_cast<const uint2*>(ts.run_items.data()), ts.run_items.size(), s);
             h_.run_ptr = std::move(ts.run_ptr);
-            drun_cnt_.alloc(1 + plan_.ntb + static_cast<size_t>(plan_.ntb) * plan_.ntb + plan_.ntb);
+            // (+ cdone[ntb] and the trailing lead's ticket: TailRun::cdone, run_cdone())
+            drun_cnt_.alloc(1 + plan_.ntb + static_cast<size_t>(plan_.ntb) * plan_.ntb + plan_.ntb + plan_.ntb + 1);
             // each step's tile windows handed to the next step's pre-update as
             // they complete (kkt_dense.hip RunPub; off: the pre-update waits
             // for the whole previous step and reads S)
@@ -1167,6 +1168,7 @@ void KktDevice::alloc_numeric() {
     IPO_HIP_CHECK(hipEventCreate(&ev3_));
     IPO_HIP_CHECK(hipEventCreateWithFlags(&ev_pre_fork_, hipEventDisableTiming));
     IPO_HIP_CHECK(hipEventCreateWithFlags(&ev_pre_done_, hipEventDisableTiming));
+    IPO_HIP_CHECK(hipEventCreateWithFlags(&ev_run_reset_, hipEventDisableTiming));
     IPO_HIP_CHECK(hipStreamSynchronize(s));
 }
 
@@ -1227,8 +1229,10 @@ KktDevice::~KktDevice() {
                              "k_panel_s %ld; tail block columns repaired %ld in %ld rounds\n", tm_.factors,
                      tm_.panel_redos, tm_.redo_where[0], tm_.redo_where[1], tm_.redo_where[2], tm_.redo_where[3],
                      tm_.tail_repairs, tm_.tail_dep_rounds);
-    if (knobs_.debug_redo)
+    if (knobs_.debug_redo) {
         std::fprintf(stderr, "kkt: forward pre-passes used %ld, discarded %ld\n", pre_used_, pre_discarded_);
+        std::fprintf(stderr, "kkt: trailing leads used %ld, discarded %ld\n", lead_used_, lead_discarded_);
+    }
     if (hScal_) (void)hipHostFree(hScal_);
     if (hFlags_) (void)hipHostFree(hFlags_);
     if (ev0_) (void)hipEventDestroy(ev0_);
@@ -1237,6 +1241,7 @@ KktDevice::~KktDevice() {
     if (ev3_) (void)hipEventDestroy(ev3_);
     if (ev_pre_fork_) (void)hipEventDestroy(ev_pre_fork_);
     if (ev_pre_done_) (void)hipEventDestroy(ev_pre_done_);
+    if (ev_run_reset_) (void)hipEventDestroy(ev_run_reset_);
     for (hipEvent_t e : kev_) (void)hipEventDestroy(e);
 }
 
@@ -1486,6 +1491,10 @@ void KktDevice::enqueue_prepass(const PrePass& pre) {
     IPO_HIP_CHECK(hipEventRecord(ev_pre_done_, q));
     pre_req_ = pre;
     pre_state_ = kPreEnqueued;
+    // the lead too, behind or beside the run: launch_tail_from(0, true)
+    // enqueues it (mode 2 records ev_pre_done_ again, after it)
+    pre_lead_ = false;
+    lead_pending_ = h_.sweep.lead_end > 0 ? knobs_.lead_trail_mode(plan_.ntb) : 0;
 }
 
 // The sparse levels (gather, then panels, level by level) and the dense
@@ -1603,6 +1612,7 @@ void KktDevice::launch_tail_from(int t0, bool reset) {
     rc.ticket = drun_cnt_.get();
     rc.pdone = drun_cnt_.get() + 1;
     rc.vseq = drun_cnt_.get() + 1 + plan_.ntb;
+    rc.cdone = run_cdone();
     if (h_.paths.run_winpub) {
         if (run_epoch_ == INT_MAX) {      // (never within a process's life: one epoch per factorisation)
             IPO_HIP_CHECK(hipMemsetAsync(drun_wflag_.get(), 0, drun_wflag_.bytes(), s));
@@ -1615,9 +1625,26 @@ void KktDevice::launch_tail_from(int t0, bool reset) {
         if (!reset) IPO_HIP_CHECK(hipMemsetAsync(rc.pread + t0, 0, (plan_.ntb - t0) * sizeof(int), s));
         rc.epoch = ++run_epoch_;
     }
+    // the trailing lead beside the run (IPO_HIP_LEAD_TRAIL=2) starts once
+    // the counters above are reset
+    if (lead_pending_ == 2) IPO_HIP_CHECK(hipEventRecord(ev_run_reset_, s));
     ph_begin(s);
     launch_tail_run(pv, tail_view(), rc, s);
     ph_end(kPhTail, rc.n > 0, s);
+    // The pre-pass's forward lead in its trailing form, enqueued after the
+    // run (a failed run launch has thrown above and leaves no poller behind):
+    // behind it on this stream (1), or beside it on the pre-pass's stream
+    // (2), where ev_pre_done_ is recorded after it, so the wait before
+    // finish_pass still leaves both streams at rest.
+    if (lead_pending_) {
+        hipStream_t q = lead_pending_ == 2 ? pre_req_.stream : s;
+        if (lead_pending_ == 2) IPO_HIP_CHECK(hipStreamWaitEvent(q, ev_run_reset_, 0));
+        else IPO_HIP_CHECK(hipStreamWaitEvent(q, ev_pre_done_, 0));     // the pre-pass's gather of the tail's z
+        launch_lead_trail(pre_req_.R, q, lead_pending_ == 2);
+        if (lead_pending_ == 2) IPO_HIP_CHECK(hipEventRecord(ev_pre_done_, q));
+        pre_lead_ = true;
+        lead_pending_ = 0;
+    }
 }
 
 // The look-ahead dense tail bailed at block column tb (a pivot failed the
@@ -1781,6 +1808,7 @@ void KktDevice::solve_multi(int R, const double* dE, const double* dD, double* c
     const int m = m_, n = n_, T = T_;
     // the first pass's head and the forward steps before the tail lead: done
     // beside the factorisation (the pre-pass, joined there), or now
+    const bool pre_lead = pre_lead_;         // (take_prepass spends it)
     const bool pre = take_prepass(R, dfy, dfx);
     if (!pre && R > 0) enqueue_pass_head(R, dfy, dfx, dPart_.get(), s);
     double maxbc[2] = {0.0, 0.0}, rs[2] = {HUGE_VAL, HUGE_VAL}, rs_old[2] = {HUGE_VAL, HUGE_VAL};
@@ -1811,7 +1839,8 @@ void KktDevice::solve_multi(int R, const double* dE, const double* dD, double* c
                                dIncons_.get(), dScal_.get() + 4);
         }
         eps_cleared_ = true;
-        const size_t fwd_first = first && pre ? static_cast<size_t>(h_.sweep.split) : 0;
+        // (the pre-pass ran the tail lead too: IPO_HIP_LEAD_TRAIL)
+        const size_t fwd_first = first && pre ? static_cast<size_t>(pre_lead ? h_.sweep.lead_end : h_.sweep.split) : 0;
         if (active[0] && active[1]) rawsolve(zv(0), 2, fwd_first);
         else rawsolve(zv(active[0] ? 0 : 1), 1, fwd_first);
         eps_cleared_ = false;
@@ -1912,6 +1941,8 @@ bool KktDevice::take_prepass(int R, double* const* dfy, double* const* dfx) {
     }
     pre_state_ = kPreNone;
     pre_used_++;
+    if (pre_lead_) lead_used_++;
+    pre_lead_ = false;
     return true;
 }
 

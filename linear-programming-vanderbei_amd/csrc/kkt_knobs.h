@@ -27,6 +27,11 @@ constexpr int kTailVisitLatest = 4;
 // Entries from which a column of Q is summed by a wave (IPO_HIP_Q_LONG): the
 // long-row threshold of A's linking rows (IpmSolver, kLongRow)
 constexpr int kLongQCol = 256;
+// Helper workgroups of the trailing forward lead beside k_tail_run
+// (IPO_HIP_LEAD_HELPERS; measured: DESIGN.md 6.6)
+constexpr int kTrailHelpers = 8;
+// Block columns from which the trailing lead is on by default (IPO_HIP_LEAD_TRAIL unset)
+constexpr int kTrailMinBlocks = 4;
 
 struct KktKnobs {
     // ---- switches: the other setting is the same arithmetic in the same
@@ -64,6 +69,35 @@ struct KktKnobs {
     // grow15 within their spread -- no tail small enough to lose.
     // test_gpu_prepass.py
     bool prepass = true;
+    // IPO_HIP_LEAD_TRAIL (unset (-1): 2 for tails of at least kTrailMinBlocks
+    // block columns, else 0; set: 0, 1 or 2, anything else as unset): where the
+    // pre-pass is eligible, the factorisation also enqueues the first solve's
+    // forward tail lead, in its trailing form (k_tail_fwd_lead<R, true>, which
+    // reads a block column of the tail once k_tail_run's TailRun::cdone says
+    // it is final and gives up if the run bails): 1 behind k_tail_run on its
+    // stream, before the read-back (removes the host round trip between the
+    // two); 2 beside it on the side stream, column by column.  The solve then
+    // starts its first sweep after the lead (SweepSteps::lead_end); 0: the
+    // solve runs the lead itself, after the read-back; bitwise.  Measured on
+    // one box, alternated (dfl001, it/s, four runs each): parent 298.0-300.0,
+    // 0: 299.3-300.9, 1: 296.3-298.3, 2: 309.1-312.2 -- 2 is the default, its
+    // slowest run above the parent's fastest.  HSD solve time
+    // in ms, parent against 2, medians of three processes of ten solves:
+    // greenbea (12 block columns) 235.4 -> 232.4, 25fv47 (7) 90.2 -> 87.6,
+    // nesm (6) 353.1 -> 353.4, bnl1 (4) 89.0 -> 87.3, brandy (3) 24.4 -> 24.6,
+    // beaconfd (3) 18.8 -> 19.1: tails without a helper block (at most
+    // kLeadBlocks + 1 = 3 block columns, a lead of ~10 us) gain nothing and
+    // pay the extra event and launch, so the default leaves them alone.
+    // test_gpu_lead_trail.py, test_lead_trail.py
+    int lead_trail = -1;
+    int lead_trail_mode(int ntb) const { return lead_trail >= 0 ? lead_trail : ntb >= kTrailMinBlocks ? 2 : 0; }
+    // IPO_HIP_LEAD_HELPERS (default kTrailHelpers; max(1, v)): helper
+    // workgroups of the trailing lead beside the run (mode 2), which take the
+    // blocks by ticket.  Each holds the launch's dynamic LDS on a CU that then
+    // has no room for a k_tail_run workgroup, so fewer cost the run less; too
+    // few fall behind the lead (dfl001, 70 block columns, it/s against the
+    // parent's 299: 8 310, 4 311, 2 269, 1 193).  Bitwise.
+    int lead_helpers = kTrailHelpers;
     // IPO_HIP_CHAIN_LEAD (default on unless it parses to 0; dense tails of at
     // most kChainMaxBlocks block columns): the forward dense-tail sweep by one
     // lead workgroup + helpers (k_tail_fwd_lead); 0: the per-block chain,
@@ -236,6 +270,9 @@ struct KktKnobs {
         k.sf = flag("IPO_HIP_SF", true);
         k.overlap = flag("IPO_HIP_OVERLAP", true);
         k.prepass = flag("IPO_HIP_PREPASS", true);
+    k.lead_trail = num("IPO_HIP_LEAD_TRAIL", -1);
+    if (k.lead_trail < 0 || k.lead_trail > 2) k.lead_trail = -1;
+    k.lead_helpers = std::max(1, num("IPO_HIP_LEAD_HELPERS", kTrailHelpers));
         k.chain_lead = flag("IPO_HIP_CHAIN_LEAD", true);
         k.chain_pairs = flag("IPO_HIP_CHAIN_PAIRS", false);
         k.tail_run = flag("IPO_HIP_TAIL_RUN", true);

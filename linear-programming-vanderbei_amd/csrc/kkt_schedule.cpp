@@ -417,6 +417,12 @@ int sweep_split(const std::vector<SweepStep>& fwd) {
     return 0;
 }
 
+int sweep_lead_end(const std::vector<SweepStep>& fwd) {
+    for (size_t i = 0; i < fwd.size(); i++)
+        if (fwd[i].kind == kSwTailLead) return static_cast<int>(i) + 1;
+    return 0;
+}
+
 SweepSteps build_sweep_steps(const KktPlan& P, const KktKnobs& knobs, const KktPaths& paths, const SolveChunks& ch,
                              const SweepOrder& order, const SyncFreePlan& sf, bool blocked) {
     SweepSteps r;
@@ -455,6 +461,7 @@ SweepSteps build_sweep_steps(const KktPlan& P, const KktKnobs& knobs, const KktP
     if (range) r.bwd.push_back({kSwSyncFree, 0, static_cast<int>(sf.items_b.size()), 0, 0});
     for (int l = top - 1; l >= 0; l--) level(l, r.bwd);
     r.split = sweep_split(r.fwd);
+    r.lead_end = sweep_lead_end(r.fwd);
     return r;
 }
 

@@ -83,9 +83,16 @@ struct SweepSteps {
     // tail's factorisation (the forward pre-pass, kkt_device.h).  0: no such
     // pair in the list (no tail, a blocked tail, the per-block chain).
     int split = 0;
+    // The step after the TailLead: where a solve's first sweep starts when the
+    // pre-pass also ran the lead, behind or beside the dense tail's factor
+    // (IPO_HIP_LEAD_TRAIL, kkt_device.h).  Non-zero exactly when the list has
+    // a TailLead.
+    int lead_end = 0;
 };
 // the rule of SweepSteps::split, on any forward list
 int sweep_split(const std::vector<SweepStep>& fwd);
+// the rule of SweepSteps::lead_end
+int sweep_lead_end(const std::vector<SweepStep>& fwd);
 // kernel launches of a list: Chunked two, every other step one
 int sweep_launches(const std::vector<SweepStep>& steps);
 
@@ -209,6 +216,14 @@ std::vector<SlotRec> build_slot_records(const KktPlan& P, const std::vector<int>
 // panel's own pre-update.  visit_hi: the end of the chunk launch t applies to
 // column c (<= 0: none).
 constexpr inline int visit_hi(int t, int c, int K) { return c - 1 - K * (c - 1 - t); }
+// The count of TailRun::cdone[t] at which block column t of a tail of nt
+// columns is readable while k_tail_run goes on (the trailing forward lead
+// waits for it): every panel item of step t in tail_run_schedule signals once
+// -- the step's panel workgroups, kkt_dense.hip tail_gp.
+constexpr inline int lead_col_target(int nt, int t) {
+    return (nt - t * kPanelCols + kTileRows - 1) / kTileRows - 1 > 1 ? (nt - t * kPanelCols + kTileRows - 1) / kTileRows - 1
+                                                                      : 1;
+}
 
 // visit tiles of launch t (tail of ntb block columns, chunks of K blocks)
 int tail_visit_tiles(int ntb, int t, int K);

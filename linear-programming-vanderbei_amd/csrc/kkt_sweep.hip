@@ -1324,9 +1324,12 @@ __device__ double g_lead_stats[8][4];
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t tail_rsrc(const double* S) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(S), 0, 0x7fffffff, 0x00020000);
 }
+// (SC1: an sc1 load, which bypasses the CU's L1 -- the trailing form's reads
+// of what k_tail_run stores meanwhile; aux bit 4 is sc1 on gfx942 / gfx950)
+template <bool SC1 = false>
 __device__ __forceinline__ double buf_ld(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
     typedef int i32x2 __attribute__((ext_vector_type(2)));
-    const i32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0);
+    const i32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, SC1 ? 16 : 0);
     return __builtin_bit_cast(double, v);
 }
 constexpr int kLeadNT = 448;
@@ -1342,13 +1345,109 @@ __device__ __forceinline__ void lds_sync() {     // LDS-only barrier: global sto
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// The trailing form (TRAIL; IPO_HIP_LEAD_TRAIL, kkt_device.h): the same
+// sweep launched behind or beside the dense tail's factor k_tail_run instead
+// of after its read-back.  It reads block column c of the tail (the tiles
+// L(i, c), the L11' of block c, its live marks) only once the run's counter
+// cdone[c] has reached lead_col_target(nt, c): every panel workgroup of step
+// c adds itself there after its last store of the step (TailRun::cdone; sc1
+// stores, every wave's vmcnt(0), a barrier, one agent-scope add), and every
+// such read here is an sc1 load issued after the poll that saw the count
+// (MI355X_MICROARCH.md's hand-off table, first row, as k_tail_run's own).
+// The lead's product waves wait for column min(i + 2, ntb - 1) before step
+// i's loads (columns 0 and 1 before the first), each helper product wave for
+// the columns of its batch.  Arithmetic, order, granules, V.z and
+// p.incons are the other form's: with every counter complete at the start
+// (the launch behind the run) the sweep is that form's, bitwise.
+// Helpers: the grid has 1 + H workgroups, H <= ntb - 1 - K; a helper that has
+// published block i's partial draws the next ticket (ticket k >= 1 is block
+// K + k) until the blocks are out, so a few workgroups, not ntb, sit beside
+// the run.  The launch's ticket counter starts at zero (tbase = 0; the run's
+// counter reset clears it), so a launch that aborts leaves nothing to
+// account for.
+// Termination.  Every wait of this form is one of
+//   (a) a poll of cdone[c] (col_wait),
+//   (b) a helper's wait for the lead's z granules (gran_wait_bail),
+//   (c) the lead's wait for a helper's partial (the loop in step()),
+// and each of them also reads the run's bail word p.flags[2] on every trip
+// and gives up when it is non-zero.  k_tail_run ends short of completing a
+// column only through a panel that bails, which raises flags[2] before it
+// posts (panel_w_body: the zero test of a first pass, and a DEP pass's
+// contradicted speculation, flags[1] bit 16, alike), or through items that
+// skip themselves because they read flags[2] set (run_wait, pre_wait): so
+// either every counter completes or flags[2] becomes and stays non-zero
+// while this launch lives (the host clears it only after both streams are at
+// rest).  With the counters complete, (b) and (c) are the other form's
+// waits: ticket k's block is held by a running workgroup once tickets < k
+// are drawn, a helper holding block b waits only for z_j, j < b - K, which
+// the lead publishes without waiting for any block >= b, and the lead at
+// step i only for the partial of block i + 1.  A wave that gives up sets the
+// workgroup's abort word in LDS and goes on to the next barrier B; every
+// wave reads the word after each B and returns there, so no wave is left at
+// a barrier and no workgroup waits for a granule of one that left -- its
+// own polls read flags[2] too.  An aborted launch's z, granules and partials
+// are incomplete; the factorisation it trailed has bailed, so its pre-pass
+// is dropped and the normal pass rewrites them (a later epoch).
+#ifndef IPO_TRAIL_SLEEP
+#define IPO_TRAIL_SLEEP 16     // ~1024 clocks between polls: the run takes ~26 us per column
+#endif
+// one wave: until cdone[c] >= lead_col_target(nt, c) (seen: a value loaded
+// earlier, to hide the first round trip); false: the run bailed meanwhile
+__device__ __forceinline__ bool col_wait(const int* cdone, const int* bailp, int nt, int c, int seen) {
+    const int need = lead_col_target(nt, c);
+    int ok = 1;
+    seen = __builtin_amdgcn_readfirstlane(seen);
+    while (seen < need) {
+        if (__builtin_amdgcn_readfirstlane(sc1_load_int(bailp)) != 0) {
+            ok = 0;
+            break;
+        }
+        __builtin_amdgcn_s_sleep(IPO_TRAIL_SLEEP);
+        seen = __builtin_amdgcn_readfirstlane(sc1_load_int(cdone + c));
+    }
+    asm volatile("" ::: "memory");     // the column's loads stay behind the poll
+    return ok != 0;
+}
+// gran_wait that gives up (false) when the run has bailed
 template <int R>
+__device__ __forceinline__ bool gran_wait_bail(const gran_t* g, unsigned epoch, int lane, int nr, double (&v)[R],
+                                               const int* bailp) {
+    for (;;) {
+        bool ok = true;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            if (lane < nr) {
+                const gran_t* q = g + ((size_t)r * 64 + lane) * 2;
+                const unsigned long long lo = __hip_atomic_load(const_cast<gran_t*>(q), __ATOMIC_RELAXED,
+                                                                __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned long long hi = __hip_atomic_load(const_cast<gran_t*>(q + 1), __ATOMIC_RELAXED,
+                                                                __HIP_MEMORY_SCOPE_AGENT);
+                ok &= (lo >> 32) == epoch && (hi >> 32) == epoch;
+                v[r] = __longlong_as_double(static_cast<long long>(((hi & 0xffffffffull) << 32) | (lo & 0xffffffffull)));
+            } else {
+                v[r] = 0.0;
+            }
+        }
+        if (__all(ok)) return true;
+        if (__builtin_amdgcn_readfirstlane(sc1_load_int(bailp)) != 0) return false;
+        __builtin_amdgcn_s_sleep(IPO_POLL_SLEEP);
+    }
+}
+// dynamic LDS of the trailing form: the lead's two L11 buffers, z history,
+// reduction scratch and marks, then the abort word
+constexpr size_t kLeadTrailLds =
+    (2 * PC * (PC + 1) + kLeadBlocks * 2 * PC + 2 * 4 * 64) * sizeof(double) + 2 * PC * sizeof(int) + 64;
+
+template <int R, bool TRAIL = false>
 __global__ void __launch_bounds__(kLeadNT)
 k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__ epsp, gran_t* __restrict__ gran,
-                gran_t* __restrict__ pgran, unsigned epoch, int* __restrict__ ticket, int tbase) {
+                gran_t* __restrict__ pgran, unsigned epoch, int* __restrict__ ticket, int tbase,
+                const int* __restrict__ cdone) {
     extern __shared__ double lds[];
     constexpr int K = kLeadBlocks;
     const int nt = tv.nt, tc = tv.tc, ntb = tv.ntb;
+    const int* bailp = p.flags + 2;
+    int* const abort_p = reinterpret_cast<int*>(lds + 2 * PC * (PC + 1) + K * 2 * PC + 2 * 4 * 64) + 2 * PC;
     // waves: 0 solves (right-hand side 0; 6, on SIMD 2, solves 1 when R = 2:
     // two independent chains at one wave each); 1, 2, 3 and 5 are column
     // groups 0-3; 4 (which would share wave 0's SIMD) leaves at once
@@ -1362,11 +1461,16 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
     // the grid drains on any share of the CUs (co-tenant kernels, shards on
     // one device) without relying on dispatch order (ADVICE/VERDICT r04)
     __shared__ int role_sh;
-    if (tid == 0) role_sh = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - tbase;
+    if (tid == 0) {
+        role_sh = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - tbase;
+        if constexpr (TRAIL) *abort_p = 0;
+    }
     __syncthreads();
-    const int role = role_sh;
+    int role = role_sh;
     if (wv == 4 || (wv == 6 && (R == 1 || role > 0))) return;
-    if (role > 0) {              // helper of block i
+    // helper of block i = role + K (TRAIL: then of the blocks of further tickets)
+    while (role > 0) {
+        if (TRAIL && role + K >= ntb) return;
         const int i = role + K, k0 = i * PC, nc = min(PC, nt - k0), jend = i - K;
         double* zb = lds;        // zb[(b R + r) PC + c]
         const __amdgpu_buffer_rsrc_t rs = tail_rsrc(tv.S);
@@ -1378,24 +1482,41 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
         for (int j0 = 0; j0 < jend; j0 += kHelpBatch) {
             double t[kHelpBatch][16];
             if (wv > 0) {
+                if constexpr (TRAIL) {     // the batch's columns readable
+                    bool go = true;
+                    for (int b = 0; b < kHelpBatch && go; b++) {
+                        const int c = min(j0 + b, jend - 1);
+                        go = col_wait(cdone, bailp, nt, c, sc1_load_int(cdone + c));
+                    }
+                    if (!go && lane == 0) *abort_p = 1;
+                }
 #pragma unroll
                 for (int b = 0; b < kHelpBatch; b++) {
                     const int s0 = (min(j0 + b, jend - 1) * PC + g16) * nt8;
 #pragma unroll
-                    for (int q = 0; q < 16; q++) t[b][q] = buf_ld(rs, voff, s0 + q * nt8);
+                    for (int q = 0; q < 16; q++) t[b][q] = buf_ld<TRAIL>(rs, voff, s0 + q * nt8);
                 }
             } else {
+                bool gone = false;     // (TRAIL) the run bailed: no further wait
 #pragma unroll
                 for (int b = 0; b < kHelpBatch; b++) {
-                    if (j0 + b < jend) {
+                    if (j0 + b < jend && !gone) {
                         double zj[R];
-                        gran_wait<R>(gran + (size_t)(j0 + b) * R * 128, epoch, lane, PC, zj);
+                        if constexpr (TRAIL) {
+                            if (!gran_wait_bail<R>(gran + (size_t)(j0 + b) * R * 128, epoch, lane, PC, zj, bailp)) {
+                                if (lane == 0) *abort_p = 1;
+                                gone = true;
+                            }
+                        } else {
+                            gran_wait<R>(gran + (size_t)(j0 + b) * R * 128, epoch, lane, PC, zj);
+                        }
 #pragma unroll
                         for (int r = 0; r < R; r++) zb[(b * R + r) * PC + lane] = zj[r];
                     }
                 }
             }
             lds_sync();
+            if (TRAIL && *abort_p) return;
             if (wv > 0) {
 #pragma unroll
                 for (int b = 0; b < kHelpBatch; b++) {
@@ -1414,7 +1535,12 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
 #pragma unroll
             for (int r = 0; r < R; r++) gran_put(part_slot(pgran, i, R, r, g, lane), epoch, acc[r]);
         }
-        return;
+        if constexpr (!TRAIL) return;
+        // the next block, by ticket (every wave read role_sh before the
+        // batch loop's barriers: jend >= 1)
+        if (tid == 0) role_sh = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - tbase;
+        lds_sync();
+        role = role_sh;
     }
     double(*Ls)[PC][PC + 1] = reinterpret_cast<double(*)[PC][PC + 1]>(lds);     // two buffers
     double* zh = lds + 2 * PC * (PC + 1);     // z of the last K blocks: zh[((j % K) R + r) PC + c]
@@ -1430,6 +1556,7 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
         long long sa = 0, st = 0, sb = 0;
 #endif
         lds_sync();                                                      // B_{-1}
+        if (TRAIL && *abort_p) return;
         for (int i = 0; i < ntb; i++) {
             LEAD_T(t0);
             const int k0 = i * PC, nc = min(PC, nt - k0);
@@ -1452,6 +1579,7 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
             zh[((i % K) * R + rs) * PC + lane] = lane < nc ? zr[0] : 0.0;
             zown[0] = znext;
             lds_sync();                                                  // B_i
+            if (TRAIL && *abort_p) return;
 #ifdef IPO_LEAD_STAMPS
             LEAD_T(t3);
             sa += t1 - t0; st += t2 - t1; sb += t3 - t2;
@@ -1478,7 +1606,7 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
         for (int b = 0; b < K; b++) {
             const int s0 = (max(i - K + b, 0) * PC + g16) * nt8;
 #pragma unroll
-            for (int q = 0; q < 16; q++) t[b][q] = buf_ld(rs, voff, s0 + q * nt8);
+            for (int q = 0; q < 16; q++) t[b][q] = buf_ld<TRAIL>(rs, voff, s0 + q * nt8);
         }
     };
     // L11 of block i (stage_l11's rows r = g + 4q of Ls[r][c] = L(r, c), c < r)
@@ -1490,9 +1618,10 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
         for (int q = 0; q < 16; q++) {
             const int r = g + 4 * q;
             const bool ok = r < nc && lane < r;
-            t[q] = buf_ld(rs, ok ? voff : 0, min(k0 + r, nt - 1) * nt8);   // masked when stored
+            t[q] = buf_ld<TRAIL>(rs, ok ? voff : 0, min(k0 + r, nt - 1) * nt8);   // masked when stored
         }
-        lvv = p.live[tc + k0 + min(pl, nc - 1)];
+        if constexpr (TRAIL) lvv = sc1_load_int(p.live + tc + k0 + min(pl, nc - 1));
+        else lvv = p.live[tc + k0 + min(pl, nc - 1)];
     };
     auto l11_store = [&](int i, const double(&t)[16], int lvv) {
         const int nc = min(PC, nt - i * PC);
@@ -1521,15 +1650,24 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
     long long pw = 0, p3 = 0, p4 = 0;
     int polls = 0;
 #endif
+    if constexpr (TRAIL) {          // columns 0 and 1 readable
+        const int c1 = min(1, ntb - 1);
+        const int s0 = sc1_load_int(cdone), s1 = sc1_load_int(cdone + c1);
+        if (!(col_wait(cdone, bailp, nt, 0, s0) && col_wait(cdone, bailp, nt, c1, s1)) && lane == 0) *abort_p = 1;
+    }
     l11_load(0, lA, vA);
     l11_store(0, lA, vA);
     load_tiles(min(1, ntb - 1), tB);
     l11_load(min(1, ntb - 1), lB, vB);
     part_load(min(1, ntb - 1));
     lds_sync();                                                          // B_{-1}
+    if (TRAIL && *abort_p) return;
     // cur / lcur: step i's tiles (and the L11 slot to refill), nxt / lnxt: step i+1's
     auto step = [&](int i, double(&cur)[K][16], double(&nxt)[K][16], double(&lcur)[16], int& vcur,
                     double(&lnxt)[16], int& vnxt) {
+        // TRAIL: column min(i + 2, ntb - 1)'s count, loaded a phase before it is tested
+        int cseen = 0;
+        if constexpr (TRAIL) cseen = sc1_load_int(cdone + min(i + 2, ntb - 1));
         double acc[R];
 #pragma unroll
         for (int r = 0; r < R; r++) acc[r] = pre[r];
@@ -1553,6 +1691,12 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
 #pragma unroll
                     for (int r = 0; r < R; r++) ok &= (praw[r][0] >> 32) == epoch && (praw[r][1] >> 32) == epoch;
                     if (__all(ok)) break;
+                    if constexpr (TRAIL) {             // its helper gave up: so does the lead
+                        if (__builtin_amdgcn_readfirstlane(sc1_load_int(bailp)) != 0) {
+                            if (lane == 0) *abort_p = 1;
+                            break;
+                        }
+                    }
 #ifdef IPO_LEAD_STAMPS
                     polls++;
 #endif
@@ -1589,6 +1733,9 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
         // step i+2's loads, unconditional (clamped in range: a conditional
         // load would keep the old registers live across the branch)
         const int i2 = min(i + 2, ntb - 1);
+        if constexpr (TRAIL) {
+            if (!col_wait(cdone, bailp, nt, i2, cseen) && lane == 0) *abort_p = 1;
+        }
         load_tiles(i2, cur);
         l11_load(i2, lcur, vcur);
         part_load(i2);
@@ -1597,11 +1744,12 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
         p3 += u2 - u0; p4 += u3 - u2;
 #endif
         lds_sync();                                                      // B_i
+        return !(TRAIL && *abort_p);
     };
     int i = 0;
     for (; i + 1 < ntb; i += 2) {      // two steps per trip, unconditionally (no register merges)
-        step(i, tA, tB, lA, vA, lB, vB);
-        step(i + 1, tB, tA, lB, vB, lA, vA);
+        if (!step(i, tA, tB, lA, vA, lB, vB)) return;
+        if (!step(i + 1, tB, tA, lB, vB, lA, vA)) return;
     }
     if (i < ntb) step(i, tA, tB, lA, vA, lB, vB);
 #ifdef IPO_LEAD_STAMPS
@@ -2122,7 +2270,9 @@ void KktDevice::raise_sweep_lds(bool sync_free) {
                {reinterpret_cast<const void*>(&k_tail_bwd_pair<1>), kPairBwdLds},
                {reinterpret_cast<const void*>(&k_tail_bwd_pair<2>), kPairBwdLds},
                {reinterpret_cast<const void*>(&k_tail_fwd_lead<1>), kChainLds},
-               {reinterpret_cast<const void*>(&k_tail_fwd_lead<2>), kChainLds}});
+               {reinterpret_cast<const void*>(&k_tail_fwd_lead<2>), kChainLds},
+               {reinterpret_cast<const void*>(&k_tail_fwd_lead<1, true>), static_cast<int>(kLeadTrailLds)},
+               {reinterpret_cast<const void*>(&k_tail_fwd_lead<2, true>), static_cast<int>(kLeadTrailLds)}});
 }
 
 // Per-level summary of the last forward sync-free sweep's stamps (10 ns
@@ -2303,7 +2453,7 @@ int KktDevice::run_sweep_steps(const std::vector<SweepStep>& steps, bool forward
             lead_ticket_next_ += grid;
             hipLaunchKernelGGL(k_tail_fwd_lead<R>, dim3(grid), dim3(kLeadNT), kChainLds, s, pv, tv, V, epsp,
                                dChainGran_.get(), dChainGran_.get() + static_cast<size_t>(plan_.ntb) * 2 * 128,
-                               ++chain_epoch_, dlead_ticket_.get(), tb);
+                               ++chain_epoch_, dlead_ticket_.get(), tb, static_cast<const int*>(nullptr));
 #ifdef IPO_LEAD_STAMPS
             if (chain_epoch_ % 64 == 41) {
                 double st[8][4];
@@ -2361,6 +2511,31 @@ void KktDevice::run_prepass_steps(int R, hipStream_t q) {
     const size_t split = static_cast<size_t>(h_.sweep.split);
     if (R == 2) run_sweep_steps<2>(h_.sweep.fwd, true, dZ_.get(), epsp, 0, split, q);
     else run_sweep_steps<1>(h_.sweep.fwd, true, dZ_.get(), epsp, 0, split, q);
+}
+
+// The forward tail lead in its trailing form (k_tail_fwd_lead<R, true>;
+// IPO_HIP_LEAD_TRAIL, kkt_device.h) for the pre-pass's R right-hand sides in
+// dZ_, on s: behind k_tail_run on its own stream, with one helper per block
+// as the other form, or beside it on the pre-pass's stream, with at most
+// knobs_.lead_helpers helper workgroups that take the blocks by ticket, so
+// that few CUs hold a poller's LDS while the run's visits want them.  Its
+// ticket follows TailRun::cdone in drun_cnt_ (zeroed with the run's counters).
+void KktDevice::launch_lead_trail(int R, hipStream_t s, bool beside) {
+    const PlanView pv = plan_view();
+    const TailView tv = tail_view();
+    const SweepVecs V{dZ_.get(), static_cast<size_t>(T_), dYbuf_.get(), h_.ybuf_stride};
+    const int nhb = std::max(0, plan_.ntb - 1 - kLeadBlocks);
+    const int grid = 1 + (beside ? std::min(nhb, knobs_.lead_helpers) : nhb);
+    const double* epsp = dScal_.get() + 4;
+    gran_t* gran = dChainGran_.get();
+    gran_t* pgran = gran + static_cast<size_t>(plan_.ntb) * 2 * 128;
+    int* cdone = run_cdone();
+    if (R == 2)
+        hipLaunchKernelGGL((k_tail_fwd_lead<2, true>), dim3(grid), dim3(kLeadNT), kLeadTrailLds, s, pv, tv, V, epsp, gran,
+                           pgran, ++chain_epoch_, cdone + plan_.ntb, 0, static_cast<const int*>(cdone));
+    else
+        hipLaunchKernelGGL((k_tail_fwd_lead<1, true>), dim3(grid), dim3(kLeadNT), kLeadTrailLds, s, pv, tv, V, epsp, gran,
+                           pgran, ++chain_epoch_, cdone + plan_.ntb, 0, static_cast<const int*>(cdone));
 }
 
 // Ticket base of the next sync-free launch of direction d over nitems items:
