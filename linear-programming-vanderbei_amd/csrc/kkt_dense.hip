@@ -1302,7 +1302,7 @@ k_panel_w(PlanView p, const int* __restrict__ fu_sup, const int* __restrict__ fu
 // one k's 64 rows is conflict-free.  ([row][k] with stride 65 had up to four
 // lanes on a bank on the operand reads.)
 constexpr int SKS = PC + 16;
-struct SyrkLds {
+struct alignas(16) SyrkLds {      // (a row pair, two doubles from an even row on, is one 16-byte access)
     double As[PC][SKS];
     double Bs[PC][SKS];
 };
@@ -1426,7 +1426,9 @@ __device__ __forceinline__ void syrk_tile512(const PlanView& p, const TailView& 
 // one read-modify-write of the tile for all of them.  Block b + 1's operands
 // are loaded into registers while block b's are multiplied from LDS (two
 // blocks in flight measured no faster: tools/ubench_tail, round 4).  On a
-// diagonal tile the |terms| of every block go to dscale (one add).
+// diagonal tile the |terms| of every block go to dscale (one add).  The tail
+// is read and written 16 bytes at a time (ld2_h / st2_h, kkt_kernels.h): 9
+// loads per thread and block where 8-byte accesses took 24.
 // SC: the persistent tail's hand-off form (sc1 loads and stores, panel_w_body).
 template <bool SC = false>
 __device__ __forceinline__ void visit_tile512(const PlanView& p, const TailView& tv, int bi, int bj, int b0, int b1,
@@ -1434,48 +1436,52 @@ __device__ __forceinline__ void visit_tile512(const PlanView& p, const TailView&
     // a bail flag of an earlier step (see k_tail_pr), read in the shadow of
     // the first operand loads
     const int bailed = bailp ? *bailp : 0;
-    const int nt = tv.nt, tid = threadIdx.x;
-    constexpr int NU = TR * PC / PNT;
+    const int nt = tv.nt, nt8 = nt * 8, tid = threadIdx.x;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    // A thread holds two adjacent rows of one column per register pair, so
+    // every access to the tail is 16 bytes wide: rows pr, pr + 1 of its
+    // tile, columns kq + 16 u (a wave reads two 512-byte column segments per
+    // load).  Byte offsets inside a block column, the same for every block:
+    // a block's loads are its buffer resource plus these, u in the scalar
+    // offset, no per-block address arithmetic.  The pair's first row is
+    // clamped to nt - 2 so that no pair reaches past the tail; a pair that
+    // starts at the tail's last row (sha / shb) is thereby read one row low
+    // and its second element taken for the first where it is used.
+    constexpr int NU = TR * PC / PNT / 2, KU = PC / NU;
+    const int pr = 2 * (lane & 31), kq = 2 * wv + (lane >> 5);
+    const int ra = bi * TR + pr, rb = bj * TR + pr;
+    const bool sha = ra == nt - 1, shb = rb == nt - 1;
+    const int offa = (min(ra, nt - 2) + kq * nt) * 8, offb = (min(rb, nt - 2) + kq * nt) * 8;
     // raw operand loads of a block: L rows of tile bi (x) and of tile bj
-    // (y), and D (d); nothing is computed from them until the block is
-    // staged into LDS -- arithmetic on a load right after it is issued
-    // makes the wave wait for it there, before the previous block's MFMA
-    // steps, and the load latency is then paid once per block
-    double rx[NU], ry[NU], rd[NU];
-    // element offsets of this thread's operands inside a block column,
-    // the same for every block (rows clamped into the tail): a block's loads
-    // are a uniform base plus these, no per-block address arithmetic (the
-    // 64-bit address of every load took ~2,000 cycles per block to issue)
-    int offa[NU], offb[NU];
-#pragma unroll
-    for (int u = 0; u < NU; u++) {
-        const int idx = tid + u * PNT, rr = idx % TR, k = idx / TR;
-        offa[u] = min(bi * TR + rr, nt - 1) + k * nt;
-        offb[u] = min(bj * TR + rr, nt - 1) + k * nt;
-    }
-    auto load = [&](int b, double (&xx)[NU], double (&yy)[NU], double (&dd)[NU]) {
+    // (y), and the block's pivots D, one per lane (d); nothing is computed
+    // from them until the block is staged into LDS -- arithmetic on a load
+    // right after it is issued makes the wave wait for it there, before the
+    // previous block's MFMA steps, and the load latency is then paid once
+    // per block
+    double2_t rx[NU], ry[NU];
+    double rd;
+    auto load = [&](int b, double2_t (&xx)[NU], double2_t (&yy)[NU], double& dd) {
         const int k0 = b * PC;
-        const double* __restrict__ Lcol = tv.S + (size_t)k0 * nt;
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(tv.S + (size_t)k0 * nt);
         const double* __restrict__ dgb = p.dg + tv.tc + k0;
         if (k0 + PC <= nt) {
 #pragma unroll
             for (int u = 0; u < NU; u++) {
-                xx[u] = ld_h<SC>(Lcol + offa[u]);
-                yy[u] = ld_h<SC>(Lcol + offb[u]);
-                dd[u] = ld_h<SC>(dgb + (tid + u * PNT) / TR);
+                xx[u] = ld2_h<SC>(rs, offa, u * KU * nt8);
+                yy[u] = ld2_h<SC>(rs, offb, u * KU * nt8);
             }
+            dd = ld_h<SC>(dgb + lane);
         } else {                       // the last, partial block column: columns clamped too
             const int kmax = nt - 1 - k0;
 #pragma unroll
             for (int u = 0; u < NU; u++) {
-                const int idx = tid + u * PNT, k = idx / TR, kc = min(k, kmax);
-                xx[u] = ld_h<SC>(Lcol + offa[u] - (k - kc) * nt);
-                yy[u] = ld_h<SC>(Lcol + offb[u] - (k - kc) * nt);
-                dd[u] = ld_h<SC>(dgb + kc);
+                const int k = kq + u * KU, back = (k - min(k, kmax)) * nt8;
+                xx[u] = ld2_h<SC>(rs, offa - back, u * KU * nt8);
+                yy[u] = ld2_h<SC>(rs, offb - back, u * KU * nt8);
             }
+            dd = ld_h<SC>(dgb + min(lane, kmax));
         }
     };
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int wr = (wv & 1) * 32, wc = (wv >> 1) * 16;
     const int li = lane & 15, lk = lane >> 4;
     const bool diag_tile = bi == bj;
@@ -1485,30 +1491,39 @@ __device__ __forceinline__ void visit_tile512(const PlanView& p, const TailView&
     double as = 0.0;
     load(b0, rx, ry, rd);
     // the tile's own entries (no other workgroup of the launch touches
-    // them), read now so their latency hides under the products; column-
-    // coalesced (wave wv holds columns wv, wv + 8, ..., lane = row: one
-    // 512-byte column segment per load), the products come to this layout
-    // through LDS at the end
-    double old[8];
-    const int rgl = bi * TR + lane;
+    // them), read now so their latency hides under the products, in the
+    // operands' layout (rows pr, pr + 1 of tile columns kq + 16 u); the
+    // products come to this layout through LDS at the end.  A masked element
+    // (past the tail, or above the diagonal of a diagonal tile) is read with
+    // its pair but never stored.
+    double2_t old[NU];
+    const __amdgpu_buffer_rsrc_t rt = buf_rsrc(tv.S + (size_t)bj * TR * nt);
+    auto own_ok = [&](int u, int e) {
+        const int cc = kq + u * KU;
+        return ra + e < nt && bj * TR + cc < nt && !(diag_tile && cc > pr + e);
+    };
 #pragma unroll
-    for (int u = 0; u < 8; u++) {
-        const int cc = wv + 8 * u, cg = bj * TR + cc;
-        const bool ok = rgl < nt && cg < nt && !(diag_tile && cc > lane);
-        old[u] = ld_h<SC>(tv.S + (ok ? rgl + (size_t)cg * nt : 0));
-    }
+    for (int u = 0; u < NU; u++) old[u] = ld2_h<SC>(rt, own_ok(u, 0) || own_ok(u, 1) ? offa + u * KU * nt8 : 0, 0);
     if (bailed && bailed - 1 < bt) return;
     // block b: operands from registers into LDS, block b + 1's loads into
     // the freed registers, then block b's MFMA steps
-    auto step = [&](int b, double (&xx)[NU], double (&yy)[NU], double (&dd)[NU]) {
+    auto step = [&](int b, double2_t (&xx)[NU], double2_t (&yy)[NU], double& dd) {
         VISIT_STAMP(b - b0, 0);
         const int nc = min(PC, nt - b * PC);
 #pragma unroll
         for (int u = 0; u < NU; u++) {
-            const int idx = tid + u * PNT, rr = idx % TR, k = idx / TR;
-            const bool oka = k < nc && bi * TR + rr < nt, okb = k < nc && bj * TR + rr < nt;
-            L.As[k][rr] = oka ? xx[u] : 0.0;
-            L.Bs[k][rr] = okb ? yy[u] * dd[u] : 0.0;    // W = L21 D of block b, formed as its panel forms it (bitwise)
+            const int k = kq + u * KU;
+            // column k's pivot: lanes 0..31 hold column 2 wv + 16 u, lanes 32..63 the next
+            const double d0 = lane_bcast(dd, 2 * wv + u * KU), d1 = lane_bcast(dd, 2 * wv + u * KU + 1);
+            const double d = lane >> 5 ? d1 : d0;
+            const double x0 = sha ? xx[u].y : xx[u].x, y0 = shb ? yy[u].y : yy[u].x;
+            double2_t va, vb;
+            va.x = k < nc && ra < nt ? x0 : 0.0;
+            va.y = k < nc && ra + 1 < nt ? xx[u].y : 0.0;
+            vb.x = k < nc && rb < nt ? y0 * d : 0.0;           // W = L21 D of block b, formed as its panel forms it (bitwise)
+            vb.y = k < nc && rb + 1 < nt ? yy[u].y * d : 0.0;
+            *reinterpret_cast<double2_t*>(&L.As[k][pr]) = va;
+            *reinterpret_cast<double2_t*>(&L.Bs[k][pr]) = vb;
         }
         VISIT_STAMP(b - b0, 1);
         __syncthreads();
@@ -1529,9 +1544,14 @@ __device__ __forceinline__ void visit_tile512(const PlanView& p, const TailView&
         for (int i = 0; i < 4; i++) L.As[wc + (lane & 15)][wr + a * 16 + (lane >> 4) + 4 * i] = acc[a][i];
     __syncthreads();
 #pragma unroll
-    for (int u = 0; u < 8; u++) {
-        const int cc = wv + 8 * u, cg = bj * TR + cc;
-        if (rgl < nt && cg < nt && !(diag_tile && cc > lane)) st_h<SC>(tv.S + rgl + (size_t)cg * nt, old[u] - L.As[cc][lane]);
+    for (int u = 0; u < NU; u++) {
+        const int cc = kq + u * KU;
+        const bool ok0 = own_ok(u, 0), ok1 = own_ok(u, 1);
+        const double2_t pv = *reinterpret_cast<const double2_t*>(&L.As[cc][pr]);
+        double* sp = tv.S + ra + (size_t)(bj * TR + cc) * nt;
+        if (ok0 && ok1) st2_h<SC>(rt, offa + u * KU * nt8, 0, old[u] - pv);
+        else if (ok0) st_h<SC>(sp, (sha ? old[u].y : old[u].x) - pv.x);   // the tail's last row alone
+        else if (ok1) st_h<SC>(sp + 1, old[u].y - pv.y);                  // a diagonal entry, its pair's first row above the diagonal
     }
     if (diag_tile && tid < TR && bi * TR + tid < nt) {
         double* dp = p.dscale + tv.tc + bi * TR + tid;

@@ -82,6 +82,26 @@ static __device__ __forceinline__ void st_h(double* p, double v) {
     else *p = v;
 }
 
+// Two adjacent doubles in one 16-byte access (buffer_load / buffer_store
+// dwordx4; SC: with sc1, the hand-off form above): the address is the
+// resource's base + voff (per lane) + soff (wave-uniform) bytes and needs
+// dword alignment only, so a column of odd leading dimension, which starts
+// 8 bytes off a 16-byte boundary, is read the same way.  The resource checks
+// no bounds: callers clamp.
+typedef double double2_t __attribute__((ext_vector_type(2)));
+static __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const double* base) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(base), 0, 0x7fffffff, 0x00020000);
+}
+template <bool SC>
+static __device__ __forceinline__ double2_t ld2_h(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
+    return __builtin_bit_cast(double2_t, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, SC ? 16 : 0));
+}
+template <bool SC>
+static __device__ __forceinline__ void st2_h(__amdgpu_buffer_rsrc_t rs, int voff, int soff, double2_t v) {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, voff, soff, SC ? 16 : 0);
+}
+
 // value of v in lane j (j wave-uniform), via two v_readlane_b32
 static __device__ __forceinline__ double lane_bcast(double v, int j) {
     const long long b = __double_as_longlong(v);

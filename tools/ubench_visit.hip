@@ -5,7 +5,8 @@
 // CU) or of the visit alone (two per CU); "same" makes every workgroup read
 // the operands of one tile (cache-resident: the compute + LDS bound).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off \
-//         -I linear-programming-vanderbei_amd/csrc tools/ubench_visit.hip -o tools/ubench_visit
+//         [-DIPO_VISIT_STAMPS] -I linear-programming-vanderbei_amd/csrc tools/ubench_visit.hip \
+//         linear-programming-vanderbei_amd/csrc/kkt_schedule.cpp -o tools/ubench_visit
 //   tools/ubench_visit [nt]                 (the table below)
 //   tools/ubench_visit nt mode chunk G reps (one configuration: for counter passes)
 #include "../linear-programming-vanderbei_amd/csrc/kkt_dense.hip"
