@@ -150,7 +150,8 @@ struct KktKnobs {
     // 2 every launch of at most kFlatMaxChunks chunks; bitwise.  test_gpu_deep.py
     int gather_flat = 1;
     // IPO_HIP_GATHER_QUAD (default 1; 0 off): quadrant gathers (k_update_quad)
-    // on the narrow levels of deep trees
+    // on the narrow levels of deep trees; 0: the flat gather, bitwise where it
+    // splits no unit.  test_gpu_sparse_shapes.py (visits, visits_noquad)
     bool gather_quad = true;
     // IPO_HIP_SMALL_LEAVES (unset (-1): kSmallLeafMinCount, kkt_schedule.h;
     // else max(0, v); 0 never): levels with at least this many small leaves
@@ -186,21 +187,25 @@ struct KktKnobs {
     // test_gpu_panel.py, test_gpu_tail_shapes.py
     int visit_latest = kTailVisitLatest;
     // IPO_HIP_VISIT_SLOTS (default kVisitSlots; max(1, v / kSlab) slabs):
-    // k-slots per deep-tree visit, held here in slabs of kSlab
+    // k-slots per deep-tree visit, held here in slabs of kSlab.
+    // test_gpu_sparse_shapes.py (vslots16)
     int visit_slabs = kVisitSlots / kSlab;
     // IPO_HIP_MIN_CHUNK (default 64; max(kSlab, v / kSlab * kSlab)): smallest
     // split-K gather chunk in k-slots; 64 measured best of 16-256 on
-    // configs[3] and dfl001.  tools/chunk_ab.py
+    // configs[3] and dfl001.  test_gpu_sparse_shapes.py (chunk16), tools/chunk_ab.py
     int min_chunk = 64;
     // IPO_HIP_SF_WIDTH (unset (-1): 300 for factors of fewer than 2^25
     // entries, 64 above; else max(1, v)): the sync-free range holds the top
-    // levels of at most this many supernodes (kkt_paths, kkt_schedule.cpp)
+    // levels of at most this many supernodes (kkt_paths, kkt_schedule.cpp);
+    // bitwise.  test_gpu_sparse_shapes.py (sfw1)
     int sf_width = -1;
     // IPO_HIP_UPDATE_XCD (default 1024; max(0, v); 0 off): PlanView::xcd --
-    // gather launches of at least this many chunks walk them XCD by XCD
+    // gather launches of at least this many chunks walk them XCD by XCD;
+    // bitwise.  test_gpu_sparse_shapes.py (xcd1)
     int update_xcd = 1024;
     // IPO_HIP_UPDATE_OCC (default 4; atoi): 4: k_update<1, 4> (four
-    // workgroups per CU), anything else k_update<1, 1>
+    // workgroups per CU), anything else k_update<1, 1>; bitwise.
+    // test_gpu_sparse_shapes.py (occ1)
     int update_occ = 4;
     // IPO_HIP_DOT_SEGMIN (unset (-1): kSegDotLen for LPs with a vector of
     // kOrderedMaxLen entries, else 0; set: max(0, v)): RedJobs::segmin of the

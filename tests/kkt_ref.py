@@ -1,13 +1,14 @@
-"""Small synthetic LPs whose dense tail has a chosen size, and an
-extended-precision LDL' of their KKT matrix (numpy only; a plain module, no
-fixtures).
+"""Small synthetic LPs whose dense tail, or whose sparse supernodes, have a
+chosen size, and an extended-precision LDL' of their KKT matrix (numpy only;
+a plain module, no fixtures).
 
 K = [[-diag(E), A], [A', diag(D)]], y-nodes first -- the numbering perm()
 speaks of (perm[new] = old).  The reference factors K[perm][:, perm]
 right-looking in np.longdouble (x86-64: 64-bit mantissa, eps 1.08e-19), with
 no pivoting and no zero test, and solves with it; it is what both the fp64
 oracle (oracle/orc_kkt.c) and the device factor are measured against in
-tests/test_tail_shapes.py and tests/test_gpu_tail_shapes.py.
+tests/test_tail_shapes.py and tests/test_gpu_tail_shapes.py, and in
+tests/test_sparse_shapes.py and tests/test_gpu_sparse_shapes.py.
 """
 import functools
 
@@ -68,7 +69,34 @@ def rows_lp(m, n, r, seed):
     return _finish(m, n, kA, iA, A, rng)
 
 
+def blocks_lp(blocks, r, seed):
+    """A block diagonal of dense m_i x n_i blocks, blocks = ((m_i, n_i), ...),
+    over r dense linking rows, which come last: column j of block i stores
+    rows [row0_i, row0_i + m_i) and rows [m - r, m); values as in dense_lp.
+    Minimum degree turns the side of a block with the lower degree into
+    single-column leaves and the other side into one supernode per block;
+    the linking rows end on top (tests/test_sparse_shapes.py pins what each
+    (blocks, r) realises)."""
+    rng = np.random.default_rng(seed)
+    ms = sum(mi for mi, _ in blocks)
+    m, n = ms + r, sum(ni for _, ni in blocks)
+    link = np.arange(ms, m, dtype=np.int32)
+    kA, iA, A = [0], [], []
+    row0 = 0
+    for mi, ni in blocks:
+        V = rng.uniform(0.5, 1.5, (ni, mi + r)) * rng.choice([-1.0, 1.0], (ni, mi + r))
+        rows = np.concatenate([np.arange(row0, row0 + mi, dtype=np.int32), link])
+        for j in range(ni):
+            iA.append(rows)
+            A.append(V[j])
+            kA.append(kA[-1] + mi + r)
+        row0 += mi
+    return _finish(m, n, np.array(kA, np.int32), np.concatenate(iA).astype(np.int32), np.concatenate(A), rng)
+
+
 def make_lp(family, shape, seed):
+    if family == "blocks":
+        return blocks_lp(*shape, seed)
     return dense_lp(*shape, seed) if family == "dense" else rows_lp(*shape, seed)
 
 
