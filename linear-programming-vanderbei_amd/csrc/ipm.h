@@ -56,6 +56,23 @@ struct ShardSpec {
     long nz_global = 0;
 };
 
+// The slots of IpmSolver::scal_ (doubles on the device; the pinned hs_ takes
+// its read-backs at the same indices unless a copy says otherwise).
+// Slots 0 .. 4 are reused: every reduction writes its results there from
+// kIsRed on, in its jobs' order.  The iteration's opening reduction of every
+// method has the named dot products; the later ones of an iteration (the
+// directions' c'fx, b'fy, c'gx, b'gy; two squared norms; one largest ratio)
+// are read as kIsRed + k beside the job list that orders them.
+constexpr int kIsRed = 0;
+constexpr int kIsZx = 0, kIsWy = 1, kIsCx = 2, kIsBy = 3;   // z'x, w'y, c'x, b'y
+constexpr int kIsXqx = 4;       // x'Qx (run_qp)
+constexpr int kIsPhiMu = 6;     // [2] phi, mu as k_hsd_residuals reads them (k_hsd_mu)
+constexpr int kIsNorm2 = 8;     // [2] squared norms of the primal and the dual residual
+constexpr int kIsTheta = 11;    // the step length k_step reads (k_hsd_theta)
+constexpr int kIsDphi = 12;     // [2] dphi, dpsi (k_hsd_dphi) for k_hsd_directions and k_hsd_theta
+constexpr int kIsPhiNext = 14;  // [2] the next iteration's phi, psi (k_hsd_theta)
+constexpr int kIsCount = 16;
+
 // Problem uploaded to HBM once; run() iterates from the reference's start
 // point and can be called repeatedly (the bench times run()).
 // bench.py's HBM-roofline leg: the HBM-bound HSD vector kernels timed alone
@@ -124,7 +141,7 @@ class IpmSolver {
     DevBuf<double> part_, part2_, scal_, lax_;
     hipStream_t side_ = nullptr;            // mu / residuals beside the factorisation (run_hsd)
     hipEvent_t ev_step_ = nullptr, ev_side_ = nullptr;
-    double* hs_ = nullptr;       // pinned scalars
+    double* hs_ = nullptr;       // pinned scalars [kIsCount]
 };
 
 // Whole-pipeline convenience used by the C ABI: host arrays in, host out.

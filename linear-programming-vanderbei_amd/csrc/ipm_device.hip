@@ -51,8 +51,9 @@ k_hsd_residuals(int m, int n, const int* __restrict__ kAt, const int* __restrict
                 double* __restrict__ fx, double* __restrict__ gy, double* __restrict__ gx, double* __restrict__ part,
                 int mrow, int mcnt, const double* __restrict__ lax, const double* __restrict__ phimu) {
     __shared__ double sh[kResThreads / 64];
-    // phimu: {phi, mu} computed on the device (the overlapped HSD iteration;
-    // E and D are then written by k_hsd_scaling ahead of the factorisation)
+    // phimu: {phi, mu} computed on the device (scal_'s kIsPhiMu, ipm.h; the
+    // overlapped HSD iteration: E and D are then written by k_hsd_scaling
+    // ahead of the factorisation)
     const double phi = phimu ? phimu[0] : phi_h;
     const double mu = phimu ? phimu[1] : mu_h;
     const bool wde = phimu == nullptr;
@@ -86,7 +87,7 @@ k_hsd_residuals(int m, int n, const int* __restrict__ kAt, const int* __restrict
     if (threadIdx.x == 0) { part[blockIdx.x] = sr; part[kRedBlocks + blockIdx.x] = ss; }
 }
 
-// directions + ratio test (hsd.c:233-237, 249-256)
+// directions + ratio test (hsd.c:233-237, 249-256); dphip: scal_'s kIsDphi
 __global__ void __launch_bounds__(NT)
 k_hsd_directions(int m, int n, const double* __restrict__ dphip, double delta, double mu, const double* __restrict__ fx,
                  const double* __restrict__ gx, const double* __restrict__ fy, const double* __restrict__ gy,
@@ -121,7 +122,7 @@ __global__ void __launch_bounds__(NT)
 k_step(int m, int n, double theta_h, const double* __restrict__ thetap, double* __restrict__ x,
        const double* __restrict__ dx, double* __restrict__ z, const double* __restrict__ dz, double* __restrict__ y,
        const double* __restrict__ dy, double* __restrict__ w, const double* __restrict__ dw) {
-    const double theta = thetap ? *thetap : theta_h;     // device-computed step (hsd) or the host's
+    const double theta = thetap ? *thetap : theta_h;     // device-computed step (hsd: kIsTheta) or the host's
     const int i = blockIdx.x * NT + threadIdx.x;
     if (i < n) { x[i] = x[i] + theta * dx[i]; z[i] = z[i] + theta * dz[i]; }
     else if (i < n + m) { const int j = i - n; y[j] = y[j] + theta * dy[j]; w[j] = w[j] + theta * dw[j]; }
@@ -136,36 +137,38 @@ k_hsd_scaling(int m, int n, const double* __restrict__ x, const double* __restri
     else if (i < m + n) { const int j = i - m; D[j] = z[j] / x[j]; }
 }
 
-// mu of hsd.c:168 on the device, the host's expression: sc[0..3] = z'x,
-// w'y, c'x, b'y; phi / psi from sc[14..15] (dev != 0) or the arguments;
-// out: sc[6] = phi, sc[7] = mu (the residual kernel's phimu)
+// (sc: IpmSolver::scal_, its slots by name: ipm.h)
+// mu of hsd.c:168 on the device, the host's expression: reads kIsZx, kIsWy
+// (the dots z'x, w'y) and phi / psi from kIsPhiNext (dev != 0) or the
+// arguments; writes kIsPhiMu = phi, mu (the residual kernel's phimu)
 __global__ void k_hsd_mu(double* sc, double denom, double phi_h, double psi_h, int dev) {
-    const double phi = dev ? sc[14] : phi_h, psi = dev ? sc[15] : psi_h;
-    sc[6] = phi;
-    sc[7] = (sc[0] + sc[1] + phi * psi) / denom;
+    const double phi = dev ? sc[kIsPhiNext] : phi_h, psi = dev ? sc[kIsPhiNext + 1] : psi_h;
+    sc[kIsPhiMu] = phi;
+    sc[kIsPhiMu + 1] = (sc[kIsZx] + sc[kIsWy] + phi * psi) / denom;
 }
 
 // hsd.c:226-231 on the device (same operations and order as the host code
-// it replaces): sc[0..3] = c'fx, b'fy, c'gx, b'gy -> sc[12] = dphi, sc[13] = dpsi
+// it replaces): reads kIsRed's c'fx, b'fy, c'gx, b'gy; writes kIsDphi = dphi, dpsi
 __global__ void k_hsd_dphi(double* sc, double gamma, double delta, double mu, double phi, double psi) {
-    const double dphi = (sc[0] - sc[1] + gamma) / (sc[2] - sc[3] - psi / phi);
+    const double* red = sc + kIsRed;
+    const double dphi = (red[0] - red[1] + gamma) / (red[2] - red[3] - psi / phi);
     const double dpsi = delta * mu / phi - psi - (psi / phi) * dphi;
-    sc[12] = dphi;
-    sc[13] = dpsi;
+    sc[kIsDphi] = dphi;
+    sc[kIsDphi + 1] = dpsi;
 }
 
-// hsd.c:249-266: step length from the largest ratio sc[0] and dphi / dpsi;
-// sc[11] = theta, sc[14] / sc[15] = the next phi / psi (read by the host at
-// the next iteration's synchronisation)
+// hsd.c:249-266: step length from the largest ratio (kIsRed's first) and
+// kIsDphi; writes kIsTheta and kIsPhiNext, the next phi / psi (read by the
+// host at the next iteration's synchronisation)
 __global__ void k_hsd_theta(double* sc, double phi, double psi) {
-    const double dphi = sc[12], dpsi = sc[13];
-    double theta = sc[0];
+    const double dphi = sc[kIsDphi], dpsi = sc[kIsDphi + 1];
+    double theta = sc[kIsRed];
     if (theta < -dphi / phi) theta = -dphi / phi;
     if (theta < -dpsi / psi) theta = -dpsi / psi;
     theta = (0.95 / theta > 1.0) ? 1.0 : 0.95 / theta;
-    sc[11] = theta;
-    sc[14] = phi + theta * dphi;
-    sc[15] = psi + theta * dpsi;
+    sc[kIsTheta] = theta;
+    sc[kIsPhiNext] = phi + theta * dphi;
+    sc[kIsPhiNext + 1] = psi + theta * dpsi;
 }
 
 __global__ void __launch_bounds__(NT)
@@ -471,7 +474,7 @@ IpmSolver::IpmSolver(int m, int n, const int* kA, const int* iA, const double* A
     if (n == 0) c_.alloc(1);
     part_.alloc(8 * kRedBlocks);
     part2_.alloc(8 * kRedBlocks);
-    scal_.alloc(16);
+    scal_.alloc(kIsCount);
     IPO_HIP_CHECK(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
     IPO_HIP_CHECK(hipEventCreateWithFlags(&ev_step_, hipEventDisableTiming));
     IPO_HIP_CHECK(hipEventCreateWithFlags(&ev_side_, hipEventDisableTiming));
@@ -481,7 +484,7 @@ IpmSolver::IpmSolver(int m, int n, const int* kA, const int* iA, const double* A
         ax_.alloc(m_ > 0 ? m_ : 1);
         axplan_.build(m, n, kA, iA, A, knobs_.ax_blocks, stream_);
     }
-    IPO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hs_), 16 * sizeof(double), hipHostMallocDefault));
+    IPO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hs_), kIsCount * sizeof(double), hipHostMallocDefault));
     IPO_HIP_CHECK(hipStreamSynchronize(stream_));
     t_setup_ = now_s() - t0;
 }
@@ -597,9 +600,10 @@ int IpmSolver::run_hsd(const IpmOptions& opt, IpmResult* res) {
             hipLaunchKernelGGL(k_hsd_residuals, dim3(kRedBlocks), dim3(kResThreads), 0, side_, m, n, K.kAt(), K.iAt(),
                                K.At(), K.kA(), K.iA(), K.A(), b_.get(), c_.get(), x_.get(), y_.get(), w_.get(), z_.get(),
                                phi, delta, 0.0, E_.get(), D_.get(), fy_.get(), fx_.get(), gy_.get(), gx_.get(),
-                               part2_.get(), mrow(), mcnt_, lax(), static_cast<const double*>(scal_.get() + 6));
-            hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, side_, part2_.get(), 2, 0u, scal_.get() + 8);
-            IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), 16 * sizeof(double), hipMemcpyDeviceToHost, side_));
+                               part2_.get(), mrow(), mcnt_, lax(), static_cast<const double*>(scal_.get() + kIsPhiMu));
+            hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, side_, part2_.get(), 2, 0u,
+                               scal_.get() + kIsNorm2);
+            IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), kIsCount * sizeof(double), hipMemcpyDeviceToHost, side_));
             IPO_HIP_CHECK(hipEventRecord(ev_side_, side_));
             hipLaunchKernelGGL(k_hsd_scaling, dim3(gv), dim3(NT), 0, s, m, n, x_.get(), y_.get(), w_.get(), z_.get(),
                                E_.get(), D_.get());
@@ -623,22 +627,23 @@ int IpmSolver::run_hsd(const IpmOptions& opt, IpmResult* res) {
                 spec_err = std::current_exception();
             }
             IPO_HIP_CHECK(hipEventSynchronize(ev_side_));
-            if (iter > 0) { phi = hs_[14]; psi = hs_[15]; }
         } else {
             launch_reduce(j, part_.get(), scal_.get(), s);
             xsum(scal_.get(), 4, RedOp::Sum);
             IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), 4 * sizeof(double), hipMemcpyDeviceToHost, s));
             if (iter > 0)
-                IPO_HIP_CHECK(hipMemcpyAsync(hs_ + 14, scal_.get() + 14, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+                IPO_HIP_CHECK(hipMemcpyAsync(hs_ + kIsPhiNext, scal_.get() + kIsPhiNext, 2 * sizeof(double),
+                                             hipMemcpyDeviceToHost, s));
             IPO_HIP_CHECK(hipStreamSynchronize(s));
-            if (iter > 0) { phi = hs_[14]; psi = hs_[15]; }
         }
-        const double mu = (hs_[0] + hs_[1] + phi * psi) / (ng_ + mg_ + 1);
+        if (iter > 0) { phi = hs_[kIsPhiNext]; psi = hs_[kIsPhiNext + 1]; }
+        const double mu = (hs_[kIsZx] + hs_[kIsWy] + phi * psi) / (ng_ + mg_ + 1);
         // the device's mu / phi must be the host's bit for bit (NaNs included:
         // a diverging solve then takes the sequential path's status route)
-        if (overlap && (std::memcmp(&mu, &hs_[7], sizeof mu) != 0 || std::memcmp(&phi, &hs_[6], sizeof phi) != 0))
+        if (overlap && (std::memcmp(&mu, &hs_[kIsPhiMu + 1], sizeof mu) != 0 ||
+                        std::memcmp(&phi, &hs_[kIsPhiMu], sizeof phi) != 0))
             throw std::runtime_error("hsd: device mu / phi differ from the host's");
-        const double pobj = hs_[2], dobj = hs_[3];
+        const double pobj = hs_[kIsCx], dobj = hs_[kIsBy];
         if (mu < 1.0e-12) {
             if (overlap) K.restore_host_state(spec);     // the speculative factorisation is not used
             if (phi > psi) status = 0;
@@ -655,16 +660,17 @@ int IpmSolver::run_hsd(const IpmOptions& opt, IpmResult* res) {
                                mrow(), mcnt_, lax(), static_cast<const double*>(nullptr));
             hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 2, 0u, scal_.get());
             xsum(scal_.get(), 2, RedOp::Sum);
-            IPO_HIP_CHECK(hipMemcpyAsync(hs_ + 8, scal_.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-            K.factor(E_.get(), D_.get());    // synchronises the stream: hs_[8..9] have landed
+            IPO_HIP_CHECK(hipMemcpyAsync(hs_ + kIsNorm2, scal_.get() + kIsRed, 2 * sizeof(double),
+                                         hipMemcpyDeviceToHost, s));
+            K.factor(E_.get(), D_.get());    // synchronises the stream: hs_'s kIsNorm2 have landed
         } else {
             if (spec_err) std::rethrow_exception(spec_err);
             IPO_HIP_CHECK(hipStreamWaitEvent(s, ev_side_, 0));   // fy fx gy gx before the solves
         }
         const double gamma = -(1 - delta) * (dobj - pobj + psi) + psi - delta * mu / phi;
 
-        const double normr = std::sqrt(hs_[8]) / phi;
-        const double norms = std::sqrt(hs_[9]) / phi;
+        const double normr = std::sqrt(hs_[kIsNorm2]) / phi;
+        const double norms = std::sqrt(hs_[kIsNorm2 + 1]) / phi;
         if (tr) {
             std::fprintf(tr, "%8d   %14.7e  %8.1e    %14.7e  %8.1e  %8.1e \n", iter, pobj / phi + f_, normr,
                          dobj / phi + f_, norms, mu);
@@ -691,13 +697,13 @@ int IpmSolver::run_hsd(const IpmOptions& opt, IpmResult* res) {
         launch_reduce(q, part_.get(), scal_.get(), s);
         xsum(scal_.get(), 4, RedOp::Sum);
         hipLaunchKernelGGL(k_hsd_dphi, dim3(1), dim3(1), 0, s, scal_.get(), gamma, delta, mu, phi, psi);
-        hipLaunchKernelGGL(k_hsd_directions, dim3(kRedBlocks), dim3(NT), 0, s, m, n, scal_.get() + 12, delta, mu,
+        hipLaunchKernelGGL(k_hsd_directions, dim3(kRedBlocks), dim3(NT), 0, s, m, n, scal_.get() + kIsDphi, delta, mu,
                            fx_.get(), gx_.get(), fy_.get(), gy_.get(), x_.get(), z_.get(), y_.get(), w_.get(), D_.get(),
                            E_.get(), dx_.get(), dz_.get(), dy_.get(), dw_.get(), part_.get());
         hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 1, 1u, scal_.get());
         xsum(scal_.get(), 1, RedOp::Max);
         hipLaunchKernelGGL(k_hsd_theta, dim3(1), dim3(1), 0, s, scal_.get(), phi, psi);
-        hipLaunchKernelGGL(k_step, dim3(gv), dim3(NT), 0, s, m, n, 0.0, scal_.get() + 11, x_.get(), dx_.get(),
+        hipLaunchKernelGGL(k_step, dim3(gv), dim3(NT), 0, s, m, n, 0.0, scal_.get() + kIsTheta, x_.get(), dx_.get(),
                            z_.get(), dz_.get(), y_.get(), dy_.get(), w_.get(), dw_.get());
     }
     hipLaunchKernelGGL(k_unscale, dim3(gv), dim3(NT), 0, s, m, n, phi, x_.get(), z_.get(), y_.get(), w_.get());
@@ -738,8 +744,8 @@ int IpmSolver::run_hsdls(const IpmOptions& opt, IpmResult* res) {
         j.a[2] = c_.get(); j.b[2] = x_.get(); j.len[2] = n; j.op[2] = 0;
         j.a[3] = b_.get(); j.b[3] = y_.get(); j.len[3] = mcnt_; j.op[3] = 0;
         reduce(j, 4);
-        const double mu = (hs_[0] + hs_[1] + phi * psi) / (ng_ + mg_ + 1);
-        const double pobj = hs_[2], dobj = hs_[3];
+        const double mu = (hs_[kIsZx] + hs_[kIsWy] + phi * psi) / (ng_ + mg_ + 1);
+        const double pobj = hs_[kIsCx], dobj = hs_[kIsBy];
         if (mu < 1.0e-12) {                                   // hsdls.c:131-153
             if (phi > 1.0e-12) status = 0;
             else if (dobj < 0.0) status = 2;
@@ -756,8 +762,8 @@ int IpmSolver::run_hsdls(const IpmOptions& opt, IpmResult* res) {
         xsum(scal_.get(), 2, RedOp::Sum);
         IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, s));
         IPO_HIP_CHECK(hipStreamSynchronize(s));
-        const double normr = std::sqrt(hs_[0]) / phi;
-        const double norms = std::sqrt(hs_[1]) / phi;
+        const double normr = std::sqrt(hs_[kIsRed]) / phi;
+        const double norms = std::sqrt(hs_[kIsRed + 1]) / phi;
         const double gamma = -(1 - delta) * (dobj - pobj + psi) + psi - delta * mu / phi;
         if (tr) {
             std::fprintf(tr, "%8d   %14.7e  %8.1e    %14.7e  %8.1e  %8.1e \n", iter, pobj / phi + f_, normr,
@@ -781,7 +787,7 @@ int IpmSolver::run_hsdls(const IpmOptions& opt, IpmResult* res) {
         q.a[2] = c_.get(); q.b[2] = gx_.get(); q.len[2] = n; q.op[2] = 0;
         q.a[3] = b_.get(); q.b[3] = gy_.get(); q.len[3] = mcnt_; q.op[3] = 0;
         reduce(q, 4);
-        const double dphi = (hs_[0] - hs_[1] + gamma) / (hs_[2] - hs_[3] - psi / phi);
+        const double dphi = (hs_[kIsRed] - hs_[kIsRed + 1] + gamma) / (hs_[kIsRed + 2] - hs_[kIsRed + 3] - psi / phi);
         const double dpsi = delta * mu / phi - psi - (psi / phi) * dphi;
 
         hipLaunchKernelGGL(k_hsdls_directions, dim3(kRedBlocks), dim3(NT), 0, s, m, n, dphi, beta, delta, mu, fx_.get(),
@@ -792,7 +798,7 @@ int IpmSolver::run_hsdls(const IpmOptions& opt, IpmResult* res) {
         IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), sizeof(double), hipMemcpyDeviceToHost, s));
         IPO_HIP_CHECK(hipStreamSynchronize(s));
         double theta = 1.0;
-        const double tv = -hs_[0];                            // min over the vector entries
+        const double tv = -hs_[kIsRed];       // min over the vector entries
         theta = theta < tv ? theta : tv;
         const double tp = ls_step_host(phi, psi, dphi, dpsi, beta, delta, mu);
         theta = theta < tp ? theta : tp;
@@ -833,7 +839,7 @@ int IpmSolver::run_intpt(const IpmOptions& opt, IpmResult* res) {
         hipLaunchKernelGGL(k_pf_residuals, dim3(kRedBlocks), dim3(kResThreads), 0, s, m, n, K.kAt(), K.iAt(), K.At(), K.kA(),
                            K.iA(), K.A(), b_.get(), c_.get(), x_.get(), y_.get(), w_.get(), z_.get(), rho_.get(),
                            sig_.get(), part_.get(), mrow(), mcnt_, lax());
-        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 2, 0u, scal_.get() + 8);
+        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 2, 0u, scal_.get() + kIsNorm2);
         RedJobs j{};
         j.nj = 4;
         j.segmin = dot_segmin_;
@@ -843,15 +849,15 @@ int IpmSolver::run_intpt(const IpmOptions& opt, IpmResult* res) {
         j.a[3] = b_.get(); j.b[3] = y_.get(); j.len[3] = mcnt_; j.op[3] = 0;
         launch_reduce(j, part_.get(), scal_.get(), s);
         xsum(scal_.get(), 4, RedOp::Sum);
-        xsum(scal_.get() + 8, 2, RedOp::Sum);
-        IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), 10 * sizeof(double), hipMemcpyDeviceToHost, s));
+        xsum(scal_.get() + kIsNorm2, 2, RedOp::Sum);
+        IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), (kIsNorm2 + 2) * sizeof(double), hipMemcpyDeviceToHost, s));
         IPO_HIP_CHECK(hipStreamSynchronize(s));
         // intpt.c:47 keeps the printed quantities in single precision
-        const float normr = static_cast<float>(std::sqrt(hs_[8]));
-        const float norms = static_cast<float>(std::sqrt(hs_[9]));
-        const double gamma = hs_[0] + hs_[1];
-        const float pobj = static_cast<float>(hs_[2] + f_);
-        const float dobj = static_cast<float>(hs_[3] + f_);
+        const float normr = static_cast<float>(std::sqrt(hs_[kIsNorm2]));
+        const float norms = static_cast<float>(std::sqrt(hs_[kIsNorm2 + 1]));
+        const double gamma = hs_[kIsZx] + hs_[kIsWy];
+        const float pobj = static_cast<float>(hs_[kIsCx] + f_);
+        const float dobj = static_cast<float>(hs_[kIsBy] + f_);
         if (tr) {
             std::fprintf(tr, "%8d   %14.7e  %8.1e    %14.7e  %8.1e \n", iter, pobj, normr, dobj, norms);
             std::fflush(tr);
@@ -873,7 +879,7 @@ int IpmSolver::run_intpt(const IpmOptions& opt, IpmResult* res) {
         xsum(scal_.get(), 1, RedOp::Max);
         IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), sizeof(double), hipMemcpyDeviceToHost, s));
         IPO_HIP_CHECK(hipStreamSynchronize(s));
-        double theta = hs_[0];
+        double theta = hs_[kIsRed];
         theta = (r / theta > 1.0) ? 1.0 : r / theta;
         hipLaunchKernelGGL(k_step, dim3(gv), dim3(NT), 0, s, m, n, theta, static_cast<const double*>(nullptr), x_.get(), dx_.get(), z_.get(), dz_.get(),
                            y_.get(), dy_.get(), w_.get(), dw_.get());
@@ -918,7 +924,7 @@ int IpmSolver::run_qp(const IpmOptions& opt, IpmResult* res) {
         hipLaunchKernelGGL(k_qp_residuals, dim3(kRedBlocks), dim3(kResThreads), 0, s, m, n, K.kA(), K.iA(), K.A(), K.kAt(),
                            K.iAt(), K.At(), K.kQ(), K.iQ(), K.Q(), b_.get(), c_.get(), x_.get(), y_.get(), w_.get(), z_.get(), rho_.get(),
                            sig_.get(), qx_.get(), part_.get(), mrow(), lax(), K.q_long_min());
-        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 2, 0u, scal_.get() + 8);
+        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 2, 0u, scal_.get() + kIsNorm2);
         RedJobs j{};
         j.nj = 5;
         j.segmin = dot_segmin_;
@@ -928,15 +934,15 @@ int IpmSolver::run_qp(const IpmOptions& opt, IpmResult* res) {
         j.a[3] = b_.get(); j.b[3] = y_.get(); j.len[3] = m; j.op[3] = 0;
         j.a[4] = x_.get(); j.b[4] = qx_.get(); j.len[4] = n; j.op[4] = 0;     // x'Qx
         launch_reduce(j, part_.get(), scal_.get(), s);
-        IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), 10 * sizeof(double), hipMemcpyDeviceToHost, s));
+        IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), (kIsNorm2 + 2) * sizeof(double), hipMemcpyDeviceToHost, s));
         IPO_HIP_CHECK(hipStreamSynchronize(s));
         // the printed quantities in single precision, as run_intpt (intpt.c:47)
-        const float normr = static_cast<float>(std::sqrt(hs_[8]));
-        const float norms = static_cast<float>(std::sqrt(hs_[9]));
-        const double gamma = hs_[0] + hs_[1];
-        const double hxqx = 0.5 * hs_[4];
-        const float pobj = static_cast<float>(hs_[2] - hxqx + f_);
-        const float dobj = static_cast<float>(hs_[3] + hxqx + f_);
+        const float normr = static_cast<float>(std::sqrt(hs_[kIsNorm2]));
+        const float norms = static_cast<float>(std::sqrt(hs_[kIsNorm2 + 1]));
+        const double gamma = hs_[kIsZx] + hs_[kIsWy];
+        const double hxqx = 0.5 * hs_[kIsXqx];
+        const float pobj = static_cast<float>(hs_[kIsCx] - hxqx + f_);
+        const float dobj = static_cast<float>(hs_[kIsBy] + hxqx + f_);
         if (tr) {
             std::fprintf(tr, "%8d   %14.7e  %8.1e    %14.7e  %8.1e \n", iter, pobj, normr, dobj, norms);
             std::fflush(tr);
@@ -957,7 +963,7 @@ int IpmSolver::run_qp(const IpmOptions& opt, IpmResult* res) {
         hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 1, 1u, scal_.get());
         IPO_HIP_CHECK(hipMemcpyAsync(hs_, scal_.get(), sizeof(double), hipMemcpyDeviceToHost, s));
         IPO_HIP_CHECK(hipStreamSynchronize(s));
-        double theta = hs_[0];
+        double theta = hs_[kIsRed];
         theta = (r / theta > 1.0) ? 1.0 : r / theta;
         hipLaunchKernelGGL(k_step, dim3(gv), dim3(NT), 0, s, m, n, theta, static_cast<const double*>(nullptr), x_.get(), dx_.get(), z_.get(), dz_.get(),
                            y_.get(), dy_.get(), w_.get(), dw_.get());

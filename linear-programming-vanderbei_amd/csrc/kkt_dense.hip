@@ -194,7 +194,7 @@ __device__ __attribute__((noinline)) void factor_diag_block(double* dscale, doub
     for (int r = tp; r < nc; r += np)
         if (tr < r) panel[tr + (size_t)r * ld] = B[r][tr];
     for (int k = tid; k < nc; k += nthr) { p.dg[c0 + k] = dv[k]; p.live[c0 + k] = lv[k]; }
-    if (tid == 0 && ndep_sh) atomicAdd(&p.flags[0], ndep_sh);
+    if (tid == 0 && ndep_sh) atomicAdd(&p.flags[kFlagNdep], ndep_sh);
 }
 
 
@@ -485,7 +485,7 @@ k_tail_dep(PlanView p, TailView tv, int kb, const double* __restrict__ st_in, do
         if (tr < r) panel[tr + (size_t)r * ld] = B[r][tr];
     for (int k = tid; k < nc; k += NT) { p.dg[c0 + k] = dv[k]; p.live[c0 + k] = lv[k]; }
     if (tid == 0) {
-        if (ndep_sh) atomicAdd(&p.flags[0], ndep_sh);
+        if (ndep_sh) atomicAdd(&p.flags[kFlagNdep], ndep_sh);
         sti_out[2] = 1;
     }
 }
@@ -493,9 +493,9 @@ k_tail_dep(PlanView p, TailView tv, int kb, const double* __restrict__ st_in, do
 // ------------------------------------------------------------ fused panel
 // Diagonal block and the rows below it in one launch: the fast path of
 // k_diag + k_trsm (k_panel_w below).  A pivot that fails the zero test stops
-// every workgroup of the panel before it writes anything and raises
-// flags[1]: the host then redoes the factorisation with k_diag / k_trsm,
-// which own the dependent-pivot rule (ldlt.c:600-614).  (Round 1's 8-wave
+// every workgroup of the panel before it writes anything and raises its bit
+// of flags[kFlagBail] (kkt_flags.h): the host then redoes the factorisation
+// with k_diag / k_trsm, which own the dependent-pivot rule (ldlt.c:600-614).  (Round 1's 8-wave
 // one-barrier-per-column k_panel, bitwise the same, measured slower and is
 // gone.)
 constexpr int PNT = 512;
@@ -521,7 +521,7 @@ constexpr int PNT = 512;
 // a / d, a -= l (l_j d_k), |terms| of each pivot in dscale order), so the
 // factor is bitwise that of k_panel and of k_diag + k_trsm.  A pivot that
 // fails the zero test raises a flag the whole workgroup reads after the
-// phase's barrier; the panel then stops unwritten (flags[1]), as k_panel.
+// phase's barrier; the panel then stops unwritten (kFlagBail), as k_panel.
 constexpr int WIN = 16;
 constexpr int CTS = PC + 2;           // Ct row stride: 16-B aligned rows for ds_read_b128
 
@@ -775,12 +775,12 @@ struct PanelLds {
 // a column "kept" with +-1e-8 is certain from the block's rows alone; a
 // dropped one is checked by every workgroup on its own tile (win_solve).  A
 // workgroup whose tile contradicts a drop (or meets a NaN) bails as the first
-// pass would have (flags[1] bit 4 | 16, flags[2]), and the host resumes the
+// pass would have (kBailTail | kBailRestore, kFlagTailBlock), and the host resumes the
 // look-ahead from this block column (KktDevice::repair_tail) after putting
 // back what the other workgroups wrote: the DEP pass saves its tile rows and
 // workgroup 0 the block's |terms| into tv.W (unused by the look-ahead) before
 // anything is written, and workgroup 0 leaves the dependent pivots it added
-// to flags[0] in flags[3] (k_tail_restore).  Where the speculation holds (122
+// to kFlagNdep in kFlagSpecNdep (k_tail_restore).  Where the speculation holds (122
 // of the 124 dependent pivots of the oracle's dfl001_100/110/114 factors that
 // fall in the GPU's dense tail), the block costs one more panel pass instead
 // of the host round trips and relaunches of a repair; the factor is bitwise
@@ -812,7 +812,7 @@ constexpr int kRunBail = 1 << 16;
 // one lane polls until pdone counter c0 (null: none) reaches v0 and vseq
 // counter c1 (null: none) reaches v1; the workgroup joins a barrier and gets
 // false for "skip the item": step t - 1 bailed (c0's bail bit), or, while a
-// counter is short, a panel of a launch before t has bailed (flags[2]: then
+// counter is short, a panel of a launch before t has bailed (kFlagTailBlock: then
 // the counter may never complete)
 __device__ __forceinline__ bool run_wait(const int* c0, int v0, const int* c1, int v1, const int* bailp, int t,
                                          int* sh) {
@@ -1016,7 +1016,7 @@ __device__ __forceinline__ bool panel_w_body(const PlanView& p, const int* __res
                     int ok = 1;
                     for (;;) {
                         if (sc1_load_int(f0 + v) == rp.epoch && (!hasj || sc1_load_int(fj + v) == rp.epoch)) break;
-                        const int b = sc1_load_int(p.flags + 2);
+                        const int b = sc1_load_int(p.flags + kFlagTailBlock);
                         if (b && b - 1 < bt) {     // an earlier step bailed: its windows may never come
                             ok = 0;
                             break;
@@ -1056,7 +1056,7 @@ __device__ __forceinline__ bool panel_w_body(const PlanView& p, const int* __res
             PANEL_STAMP(3);
             // the visits of this panel's tiles, then its own entries (and a
             // DEP pass's saves of them)
-            if (!run_wait(rp.vd, rp.q, rp.vt, rp.q, p.flags + 2, bt, rp.sh)) return false;
+            if (!run_wait(rp.vd, rp.q, rp.vt, rp.q, p.flags + kFlagTailBlock, bt, rp.sh)) return false;
             load_own();
             dep_save();
         } else {
@@ -1169,7 +1169,7 @@ __device__ __forceinline__ bool panel_w_body(const PlanView& p, const int* __res
                         for (;;) {
                             got = sc1_load_int(rp.pread + kb - 1);
                             if (got >= need) break;
-                            const int b = sc1_load_int(p.flags + 2);
+                            const int b = sc1_load_int(p.flags + kFlagTailBlock);
                             if (b && b - 1 < kb) break;        // the launch is being abandoned
                             __builtin_amdgcn_s_sleep(1);
                         }
@@ -1229,10 +1229,10 @@ __device__ __forceinline__ bool panel_w_body(const PlanView& p, const int* __res
                           : tiny_sh != 0;
     if (fail) {
         if (tid == 0) {
-            atomicOr(&p.flags[1], fu_sup ? 2 : DEP ? 4 | 16 : 4);   // bit: where it bailed (16: restore first)
-            if (!fu_sup) atomicMax(&p.flags[2], kb + 1);   // the dense-tail block column
+            atomicOr(&p.flags[kFlagBail], fu_sup ? kBailSparse : DEP ? kBailTail | kBailRestore : kBailTail);
+            if (!fu_sup) atomicMax(&p.flags[kFlagTailBlock], kb + 1);   // the dense-tail block column
             if (DEP && !fu_sup && j == 0)                  // workgroup 0 added no dependent pivots
-                __hip_atomic_store(p.flags + 3, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(p.flags + kFlagSpecNdep, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         post(true);
         return false;
@@ -1267,9 +1267,9 @@ __device__ __forceinline__ bool panel_w_body(const PlanView& p, const int* __res
     for (int rr = 1 + wv; rr < nc; rr += PNT / 64)
         if (lane < rr) st_h<SC>(panel + lane + (size_t)rr * ld, Ct[rr][lane]);
     if (DEP && tid == 0) {
-        if (S.ndep) atomicAdd(&p.flags[0], S.ndep);
+        if (S.ndep) atomicAdd(&p.flags[kFlagNdep], S.ndep);
         if (!fu_sup)                                // taken back by k_tail_restore if a later check fails
-            __hip_atomic_store(p.flags + 3, S.ndep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(p.flags + kFlagSpecNdep, S.ndep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     PANEL_STAMP(13);
     return false;
@@ -1572,27 +1572,30 @@ constexpr size_t kTailStepLds = kTailStepLds0 > sizeof(PreLds) ? kTailStepLds0 :
 __global__ void __launch_bounds__(PNT)
 k_tail_pr(PlanView p, TailView tv, int t, int gp, int vbase) {
     __shared__ __attribute__((aligned(16))) char lds[kTailStepLds];
-    // a panel of an earlier step bailed (flags[2] = 1 + its block column;
-    // not this launch's own, whose visits must complete): the host
-    // resumes the look-ahead from there
+    // a panel of an earlier step bailed (flags[kFlagTailBlock]; not this
+    // launch's own, whose visits must complete): the host resumes the
+    // look-ahead from there
     if ((int)blockIdx.x < gp) {
         PanelLds& S = *reinterpret_cast<PanelLds*>(lds);
-        if (panel_w_body<false>(p, nullptr, nullptr, 0, tv, t, blockIdx.x, S, nullptr, t > 0, p.flags + 2, t, tv.dep)) {
+        if (panel_w_body<false>(p, nullptr, nullptr, 0, tv, t, blockIdx.x, S, nullptr, t > 0,
+                                p.flags + kFlagTailBlock, t, tv.dep)) {
             __syncthreads();           // every wave has read the first pass's verdict
-            panel_w_body<true>(p, nullptr, nullptr, 0, tv, t, blockIdx.x, S, nullptr, t > 0, p.flags + 2, t, tv.dep);
+            panel_w_body<true>(p, nullptr, nullptr, 0, tv, t, blockIdx.x, S, nullptr, t > 0, p.flags + kFlagTailBlock,
+                               t, tv.dep);
         }
         return;
     }
     if (tv.vlist) {
         const unsigned v = tv.vlist[vbase + blockIdx.x - gp];
         visit_tile512(p, tv, v & 255, (v >> 8) & 255, (v >> 16) & 255, v >> 24, *reinterpret_cast<SyrkLds*>(lds),
-                      p.flags + 2, t);
+                      p.flags + kFlagTailBlock, t);
         return;
     }
     int tile = blockIdx.x - gp, c = t + 1;
     while (tile >= tv.ntb - c) { tile -= tv.ntb - c; c++; }
     const int b1 = visit_hi(t, c, tv.vk);
-    visit_tile512(p, tv, c + tile, c, max(0, b1 - tv.vk), b1, *reinterpret_cast<SyrkLds*>(lds), p.flags + 2, t);
+    visit_tile512(p, tv, c + tile, c, max(0, b1 - tv.vk), b1, *reinterpret_cast<SyrkLds*>(lds),
+                  p.flags + kFlagTailBlock, t);
 }
 
 // ----------------------------------------- dense tail: one persistent launch
@@ -1611,7 +1614,7 @@ k_tail_pr(PlanView p, TailView tv, int t, int gp, int vbase) {
 // the CUs (a ticket is only drawn by a running workgroup).  Hand-offs: the
 // data sc1 both ways, every storing wave's vmcnt(0) and a barrier before one
 // lane's agent-scope add (MI355X_MICROARCH.md's first row).  A panel that
-// bails (flags[2]) still counts itself, so its step's visits complete as in
+// bails (kFlagTailBlock) still counts itself, so its step's visits complete as in
 // k_tail_pr; every item of a later launch reads the flag after its wait and
 // is skipped without counting, and the host repair resumes the run from
 // step tb + 1 with the counters as they are.
@@ -1624,7 +1627,7 @@ k_tail_run(PlanView p, TailView tv, TailRun rc) {
     // barrier separates a slow wave's read of the first from the second's write
     __shared__ int sh_item, sh_ok, sh_ok2;
     const int ntb = tv.ntb;
-    const int* bailp = p.flags + 2;
+    const int* bailp = p.flags + kFlagTailBlock;
     // one item per workgroup, drawn when the workgroup starts (a loop over
     // items in a persistent grid kept more registers live: 256 VGPRs and
     // spills against k_tail_pr's 218; the dispatcher starts a workgroup as
@@ -1691,8 +1694,8 @@ k_tail_run(PlanView p, TailView tv, TailRun rc) {
     if (tr && threadIdx.x == 0) tr[2] = __builtin_amdgcn_s_memrealtime();
 }
 
-// A DEP pass of block column kb failed its check in some workgroup (flags[1]
-// bit 16) after others had written: put back the tile rows and the block's
+// A DEP pass of block column kb failed its check in some workgroup
+// (kBailRestore) after others had written: put back the tile rows and the block's
 // |terms| it saved in tv.W and the dependent pivots workgroup 0 added, so the
 // host repair starts from the column as the look-ahead left it.
 __global__ void __launch_bounds__(256)
@@ -1704,8 +1707,8 @@ k_tail_restore(PlanView p, TailView tv, int kb) {
     if (blockIdx.x == 0 && c == 0) {
         if ((int)threadIdx.x < nc) p.dscale[tv.tc + k0 + threadIdx.x] = tv.W[threadIdx.x];
         if (threadIdx.x == 0) {
-            p.flags[0] -= p.flags[3];
-            p.flags[3] = 0;
+            p.flags[kFlagNdep] -= p.flags[kFlagSpecNdep];
+            p.flags[kFlagSpecNdep] = 0;
         }
     }
 }
@@ -1727,7 +1730,7 @@ k_tail_col(PlanView p, TailView tv, int t) {
 // a_r(q) -= l c_q with c_q by v_readlane -- the operations and order of
 // factor_diag_fast per entry (bitwise the same factor).  A pivot that fails
 // the zero test stops the wave before it writes anything and raises
-// flags[1], as the other fused kernels.
+// kBailSmall, as the other fused kernels their bits.
 constexpr int SNC = 16;
 
 __device__ __forceinline__ void panel_s_body(const PlanView& p, const int* __restrict__ sups, int q0, int q, int dep) {
@@ -1762,7 +1765,7 @@ __device__ __forceinline__ void panel_s_body(const PlanView& p, const int* __res
                 const bool in = lane > k && rok;
                 const bool nan = __ballot(in && a[k] != a[k]) != 0;
                 if (!dep || nan) {
-                    if (lane == 0) atomicOr(&p.flags[1], 8);
+                    if (lane == 0) atomicOr(&p.flags[kFlagBail], kBailSmall);
                     return;
                 }
                 if (__ballot(in && !(fabs(a[k]) < 1.0e+6 * 1.0e-8)) != 0) dk = (p.sign[c0 + k] < 0 ? -1.0 : 1.0) * 1.0e-8;
@@ -1790,7 +1793,7 @@ __device__ __forceinline__ void panel_s_body(const PlanView& p, const int* __res
         }
     }
     if (lane < nc) { p.dg[c0 + lane] = mydv; p.live[c0 + lane] = mylive; }
-    if (ndep && lane == 0) atomicAdd(&p.flags[0], ndep);
+    if (ndep && lane == 0) atomicAdd(&p.flags[kFlagNdep], ndep);
 }
 
 __global__ void __launch_bounds__(256)
@@ -1850,7 +1853,7 @@ k_panel_s1(PlanView p, const int* __restrict__ sups, int q0, int count, int dep)
         const bool in = lq > 0 && rok;
         const bool nan = (__ballot(in && a != a) & gmask) != 0;
         if (!dep || nan) {
-            if (lq == 0) atomicOr(&p.flags[1], 8);
+            if (lq == 0) atomicOr(&p.flags[kFlagBail], kBailSmall);
             return;
         }
         if ((__ballot(in && !(fabs(a) < 1.0e+6 * 1.0e-8)) & gmask) != 0) dk = (p.sign[c0] < 0 ? -1.0 : 1.0) * 1.0e-8;
@@ -1863,7 +1866,7 @@ k_panel_s1(PlanView p, const int* __restrict__ sups, int q0, int count, int dep)
     if (lq == 0) {
         p.dg[c0] = dk;
         p.live[c0] = alive;
-        if (ndep) atomicAdd(&p.flags[0], ndep);
+        if (ndep) atomicAdd(&p.flags[kFlagNdep], ndep);
     }
 }
 

@@ -17,6 +17,7 @@
 
 #include "hip_util.h"
 #include "exchange.h"
+#include "kkt_flags.h"
 #include "kkt_knobs.h"
 #include "kkt_plan.h"
 #include "kkt_schedule.h"
@@ -70,8 +71,38 @@ struct TailRun {
     unsigned long long* trace = nullptr;
 };
 
+// The run's counters in one allocation of words(ntb) ints: TailRun's ticket,
+// pdone[ntb], vseq[ntb * ntb], pread[ntb] and cdone[ntb], then the trailing
+// lead's ticket (launch_lead_trail), which the run's reset clears with them.
+struct RunCounters {
+    static constexpr size_t kTicket = 0, kPdone = 1;
+    static constexpr size_t vseq_at(size_t ntb) { return kPdone + ntb; }
+    static constexpr size_t pread_at(size_t ntb) { return vseq_at(ntb) + ntb * ntb; }
+    static constexpr size_t cdone_at(size_t ntb) { return pread_at(ntb) + ntb; }
+    static constexpr size_t lead_ticket_at(size_t ntb) { return cdone_at(ntb) + ntb; }
+    static constexpr size_t words(size_t ntb) { return lead_ticket_at(ntb) + 1; }
+    int *ticket, *pdone, *vseq, *pread, *cdone, *lead_ticket;
+    RunCounters(int* base, size_t ntb)
+        : ticket(base + kTicket), pdone(base + kPdone), vseq(base + vseq_at(ntb)), pread(base + pread_at(ntb)),
+          cdone(base + cdone_at(ntb)), lead_ticket(base + lead_ticket_at(ntb)) {}
+};
+static_assert(RunCounters::words(1) == 6 && RunCounters::cdone_at(1) == 4, "run counters, ntb = 1");
+static_assert(RunCounters::vseq_at(3) == 4 && RunCounters::pread_at(3) == 13 && RunCounters::cdone_at(3) == 16 &&
+                  RunCounters::lead_ticket_at(3) == 19 && RunCounters::words(3) == 20,
+              "run counters, ntb = 3: 1 + 3 + 9 + 3 + 3 + 1");
+
 // one published tile window: 16 columns of 64 rows of L, then the 16 pivots d
 constexpr int kTailPubWin = 16 * 64 + 16;
+
+// The dense-tail sweeps' granules (kkt_sweep.hip gran_put, part_slot) in one
+// allocation of words(ntb), sized for 2 right-hand sides: every block's z,
+// then from part_at(ntb) on every block's helper partials of k_tail_fwd_lead.
+struct ChainGran {
+    static constexpr size_t kZ = 2 * 64 * 2;          // per block: right-hand sides x rows x {low, high} half
+    static constexpr size_t kPart = 2 * 4 * 64 * 2;   // per block: right-hand sides x column groups x lanes x halves
+    static constexpr size_t part_at(size_t ntb) { return ntb * kZ; }
+    static constexpr size_t words(size_t ntb) { return ntb * (kZ + kPart); }
+};
 
 // (KktPhase, the device-time phases of the KKT core: kkt_schedule.h)
 struct KktTimers {
@@ -87,6 +118,21 @@ struct KktTimers {
     long tail_repairs = 0;    // dense-tail block columns redone in place (look-ahead resumed after them)
     long tail_dep_rounds = 0; // k_tail_dep launches of those repairs
 };
+
+// The slots of dScal_, one refinement pass's scalars (doubles).  The first
+// pass reads [0, kScMaxbc + 2 R) back, a later one [0, kScReadLater).
+constexpr int kScRes = 0;       // [2] the residual of each active system
+constexpr int kScEps = 4;       // [2] the sweeps' dropped-column eps per right-hand side (sweep_eps())
+constexpr int kScIncons = 6;    // dIncons_'s two ints packed into one double
+constexpr int kScReadLater = kScIncons + 1;
+constexpr int kScMaxbc = 8;     // [2 * 2] max|fx|, max|fy| per system (the first pass's maxbc)
+constexpr int kScCount = kScMaxbc + 4;
+// The slots of dFacScal_, finish_pass's read-back.
+constexpr int kFsNegMinD = 0;   // -min|d| (a max reduction)
+constexpr int kFsNdepMax = 1;   // a sharded solve: kFlagNdep and kFlagBail as doubles,
+constexpr int kFsBailMax = 2;   // ... the three of them then maximised over the shards
+constexpr int kFsFlags = 3;     // [2] the first three flag words packed as ints
+constexpr int kFsCount = kFsFlags + 2;
 
 // The Q block of ldlt.c's K (ldlt.c:253-256, 391-394) on the y-nodes:
 // K_yy = -max(E, eps) - qmax Q, Q m x m full symmetric CSC (kkt_plan.h
@@ -353,8 +399,6 @@ class KktDevice {
     hipEvent_t ev_run_reset_ = nullptr;        // mode 2: the run's counters are reset
     long lead_used_ = 0, lead_discarded_ = 0;  // (IPO_HIP_DEBUG_REDO)
     void launch_lead_trail(int R, hipStream_t s, bool beside);   // (kkt_sweep.hip)
-    // TailRun::cdone, then the trailing lead's ticket: behind pread in drun_cnt_
-    int* run_cdone() { return drun_cnt_.get() + 1 + plan_.ntb + static_cast<size_t>(plan_.ntb) * plan_.ntb + plan_.ntb; }
     DevBuf<double> dPrePart_;      // the pre-pass's maxbc partials (dPart_ is finish_pass's meanwhile)
     void enqueue_levels(const PlanView& pv, const TailView& tv, bool fused, hipStream_t s, const PrePass* pre);
     bool finish_pass(bool fused);
@@ -373,7 +417,7 @@ class KktDevice {
     DevBuf<double> dPartialTile_;
     DevBuf<TaskSrc> dusrc_, dtsrc_;   // per gather task: source panel descriptor
     DevBuf<SlotRec> dslot_rec_, dtail_slot_rec_;   // per gather k-slot record (sparse units, dense tail)
-    DevBuf<unsigned long long> dChainGran_;   // dense-tail sweep chains: z of every block as epoch-tagged granules
+    DevBuf<unsigned long long> dChainGran_;   // dense-tail sweep chains: epoch-tagged granules (ChainGran)
     int chain_epoch_ = 0;      // the chains' launch epoch (one per launch, never reused)
     DevBuf<int> dtail_task_ptr_, dtail_kslot_, dtail_kslot_ptr_;
     DevBuf<int> dlead_ticket_;         // k_tail_fwd_lead's role tickets (never reset within a run)
@@ -381,7 +425,8 @@ class KktDevice {
     DevBuf<unsigned> dvisit_list_;     // TailView::vlist (tail_visit_schedule; knobs_.visit_sched off: none)
     // the dense tail as one persistent launch (k_tail_run; knobs_.tail_run off: one launch per step)
     DevBuf<uint2> drun_items_;         // tail_run_schedule (first item of each launch: h_.run_ptr)
-    DevBuf<int> drun_cnt_;             // ticket, pdone[ntb], vseq[ntb * ntb], pread[ntb], cdone[ntb], lead ticket
+    DevBuf<int> drun_cnt_;             // RunCounters
+    RunCounters run_counters() const { return RunCounters(drun_cnt_.get(), plan_.ntb); }
     // the run's window hand-off (TailRun::pub; knobs_.tail_winpub)
     DevBuf<double> drun_pub_;          // [2 * ntb * 4 * kTailPubWin]
     DevBuf<int> drun_wflag_;           // [ntb * ntb * 4], zeroed once
@@ -396,15 +441,19 @@ class KktDevice {
     DevBuf<double> dLx_, dDg_;
     DevBuf<int> dLive_;
     DevBuf<double> dDscale_;
-    DevBuf<int> dFlags_;           // [0] ndep, [1] fused bail bits, [2] 1 + bailed tail block, [4..] node sign
+    DevBuf<int> dFlags_;           // PlanView::flags (kFlagWords, kkt_flags.h)
+    DevBuf<int> dSign_;            // PlanView::sign
     DevBuf<double> dZ_, dDy_, dDx_, dRy_, dRx_;
-    DevBuf<double> dPart_, dScal_;
-    // finish_pass's read-back (min|d| and the packed flags) has slots of its
-    // own: the pre-pass's k_perm_in2 zeroes dScal_[4..5] and its maxbc stands
-    // in dScal_[8..] while finish_pass runs
+    DevBuf<double> dPart_;
+    DevBuf<double> dScal_;         // [kScCount] a refinement pass's scalars
+    double* sweep_eps() const { return dScal_.get() + kScEps; }
+    // finish_pass's read-back has slots of its own ([kFsCount]): the pre-pass's
+    // k_perm_in2 zeroes kScEps and its maxbc stands in kScMaxbc while
+    // finish_pass runs
     DevBuf<double> dFacScal_;
-    double* hScal_ = nullptr;      // pinned
-    int* hFlags_ = nullptr;        // pinned
+    double* hScal_ = nullptr;      // pinned: the read-back of dScal_ or dFacScal_
+    int* hDepDone_ = nullptr;      // pinned: repair_tail's read-back of k_tail_dep's done word
+    FactorVerdict verdict_;        // of the last factor pass (finish_pass)
 };
 
 }  // namespace ipo

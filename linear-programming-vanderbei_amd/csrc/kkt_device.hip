@@ -62,7 +62,7 @@ k_assemble_diag(int T, int m, const int* __restrict__ perm, const double* __rest
                 double* __restrict__ Lx, int* __restrict__ live, double* __restrict__ dscale, int tail_from,
                 int* __restrict__ flags, const double* __restrict__ qdiag, double qmax) {
     const int v = blockIdx.x * NT + threadIdx.x;
-    if (v < 4) flags[v] = 0;      // the factorisation's flags (no fill launch of their own)
+    if (v < kFlagWords) flags[v] = 0;      // the factorisation's flags (no fill launch of their own)
     if (v >= T) return;
     const int old = perm[v];
     // columns >= tail_from: replicated linking rows of a non-leading shard,
@@ -1101,7 +1101,7 @@ void KktDevice::setup_tail(int cus) {
         dDepSt_.alloc(tail_dep_state_doubles(plan_.ntb));
         dDepI_.alloc(8);
         // R <= 2 right-hand sides: z of every block, then k_tail_fwd_lead's helper partials
-        dChainGran_.alloc(static_cast<size_t>(plan_.ntb) * (2 * 128 + 2 * 4 * 64 * 2));
+        dChainGran_.alloc(ChainGran::words(plan_.ntb));
         dlead_ticket_.alloc(1);
         IPO_HIP_CHECK(hipMemsetAsync(dlead_ticket_.get(), 0, sizeof(int), s));
         lead_ticket_next_ = 0;
@@ -1119,8 +1119,7 @@ void KktDevice::setup_tail(int cus) {
             static_assert(sizeof(SchedUint2) == sizeof(uint2), "SchedUint2 is uploaded as uint2");
             drun_items_.upload(reinterpret_cast<const uint2*>(ts.run_items.data()), ts.run_items.size(), s);
             h_.run_ptr = std::move(ts.run_ptr);
-            // (+ cdone[ntb] and the trailing lead's ticket: TailRun::cdone, run_cdone())
-            drun_cnt_.alloc(1 + plan_.ntb + static_cast<size_t>(plan_.ntb) * plan_.ntb + plan_.ntb + plan_.ntb + 1);
+            drun_cnt_.alloc(RunCounters::words(plan_.ntb));
             // each step's tile windows handed to the next step's pre-update as
             // they complete (kkt_dense.hip RunPub; off: the pre-update waits
             // for the whole previous step and reads S)
@@ -1142,14 +1141,9 @@ void KktDevice::alloc_numeric() {
     dDg_.alloc(T_ > 0 ? T_ : 1);
     dLive_.alloc(T_ > 0 ? T_ : 1);
     dDscale_.alloc(T_ > 0 ? T_ : 1);
-    // flags: [0] ndep, [1] fused panel bail-out bits, [2] 1 + the dense-tail
-    // block column whose look-ahead panel bailed, [4..4+T) node class sign
-    dFlags_.alloc(4 + T_);
-    {
-        std::vector<int> fl(4 + T_, 0);
-        for (int v = 0; v < T_; v++) fl[4 + v] = plan_.dsign[v];
-        dFlags_.upload(fl, s);
-    }
+    dFlags_.alloc(kFlagWords);
+    IPO_HIP_CHECK(hipMemsetAsync(dFlags_.get(), 0, dFlags_.bytes(), s));
+    dSign_.upload(plan_.dsign, s);
     dZ_.alloc(2 * (T_ > 0 ? T_ : 1));
     dDy_.alloc(2 * (m_ > 0 ? m_ : 1));
     dRy_.alloc(2 * (m_ > 0 ? m_ : 1));
@@ -1157,11 +1151,13 @@ void KktDevice::alloc_numeric() {
     dRx_.alloc(2 * (n_ > 0 ? n_ : 1));
     dIncons_.alloc(2);
     dPart_.alloc(8 * kRedBlocks);
-    dScal_.alloc(16);
-    dFacScal_.alloc(8);
+    dScal_.alloc(kScCount);
+    dFacScal_.alloc(kFsCount);
+    static_assert(kFlagReadWords * sizeof(int) <= (kFsCount - kFsFlags) * sizeof(double), "the packed flag words");
     dPrePart_.alloc(8 * kRedBlocks);
-    IPO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hScal_), 16 * sizeof(double), hipHostMallocDefault));
-    IPO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hFlags_), 8 * sizeof(int), hipHostMallocDefault));
+    IPO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hScal_), std::max(kScCount, kFsCount) * sizeof(double),
+                                hipHostMallocDefault));
+    IPO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hDepDone_), sizeof(int), hipHostMallocDefault));
     IPO_HIP_CHECK(hipEventCreate(&ev0_));
     IPO_HIP_CHECK(hipEventCreate(&ev1_));
     IPO_HIP_CHECK(hipEventCreate(&ev2_));
@@ -1234,7 +1230,7 @@ KktDevice::~KktDevice() {
         std::fprintf(stderr, "kkt: trailing leads used %ld, discarded %ld\n", lead_used_, lead_discarded_);
     }
     if (hScal_) (void)hipHostFree(hScal_);
-    if (hFlags_) (void)hipHostFree(hFlags_);
+    if (hDepDone_) (void)hipHostFree(hDepDone_);
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
     if (ev2_) (void)hipEventDestroy(ev2_);
@@ -1255,7 +1251,7 @@ PlanView KktDevice::plan_view() const {
     v.relptr = drelptr_.get(); v.rel = drel_.get();
     v.Lx = dLx_.get(); v.dg = dDg_.get(); v.live = dLive_.get();
     v.flags = dFlags_.get();
-    v.sign = dFlags_.get() + 4;
+    v.sign = dSign_.get();
     v.xcd = knobs_.update_xcd;     // gather launches of at least this many chunks walk them XCD by XCD (0: off)
     v.dscale = dDscale_.get();
     v.tau = pivot_tol_;
@@ -1348,19 +1344,16 @@ void KktDevice::factor_core(const double* dE, const double* dD, const PrePass* p
     const bool ok = factor_pass(dE, dD, use_panel_, use_panel_, pre);
     if (!ok) {
         tm_.panel_redos++;
-        for (int b = 0; b < 4; b++) tm_.redo_where[b] += (hFlags_[1] >> b) & 1;
-        // bit 16: a dependent-pivot pass of the tail failed its check (restore first)
-        const bool tail_only = (hFlags_[1] & ~16) == 4 && hFlags_[4] > 0;
-        if (repair && tail_only) repair_tail();
-        else if (!factor_pass(dE, dD, false, repair) && repair && (hFlags_[1] & ~16) == 4 && hFlags_[4] > 0)
-            repair_tail();
+        for (int b = 0; b < 4; b++) tm_.redo_where[b] += (verdict_.bail >> b) & 1;
+        if (repair && verdict_.tail_only()) repair_tail();
+        else if (!factor_pass(dE, dD, false, repair) && repair && verdict_.tail_only()) repair_tail();
     }
     tm_.factors++;
     // one occurrence per factorisation, whatever redos and repairs it took
     // (their launches and time stay in the phases: the work is priced once)
     if (timing_)
         for (int ph : {kPhGather, kPhDiag, kPhTrsm, kPhSyrk, kPhTail}) tm_.phase_count[ph]++;
-    ndep_ = xch_ ? static_cast<int>(hScal_[1]) : hFlags_[0];
+    ndep_ = verdict_.ndep_all;
     // the pre-pass stands if the first pass did (no redo, no repair) and no
     // pivot was dropped: it ran with eps = 0, which only a factor without
     // dropped columns never reads (rawsolve, ldlt.c:446)
@@ -1368,7 +1361,7 @@ void KktDevice::factor_core(const double* dE, const double* dD, const PrePass* p
         if (ok && ndep_ == 0) pre_state_ = kPreValid;
         else drop_prepass();
     }
-    if (-hScal_[0] < 1.0e-14) epsdiag_ *= 10;
+    if (verdict_.min_d < 1.0e-14) epsdiag_ *= 10;
     // developer diagnostics (IPO_HIP_EPSDIAG_MAX, tools/status_loss_probe.py):
     // a cap on the growth above, to measure what a stalled solve owes to it
     if (knobs_.epsdiag_max > 0.0 && epsdiag_ > knobs_.epsdiag_max) epsdiag_ = knobs_.epsdiag_max;
@@ -1377,7 +1370,7 @@ void KktDevice::factor_core(const double* dE, const double* dD, const PrePass* p
 // One numeric factorisation, the sparse levels by the fused kernels (fused)
 // or the per-phase ones, the dense tail by the look-ahead (tail_fused) or
 // the per-phase kernels; returns false when fused kernels bailed out
-// (flags[1] says where; nothing of a bailed part may then be used).
+// (verdict_.bail says where; nothing of a bailed part may then be used).
 bool KktDevice::factor_pass(const double* dE, const double* dD, bool fused, bool tail_fused, const PrePass* pre) {
     hipStream_t s = stream_;
     if (timing_) IPO_HIP_CHECK(hipEventRecord(ev0_, s));
@@ -1456,7 +1449,7 @@ bool KktDevice::prepass_eligible(const PrePass* pre, bool fused, bool tail_fused
 }
 
 // The head of a solve's first refinement pass for R right-hand sides, on s:
-// maxbc_r = MAX(maxv(fx_r), maxv(fy_r)) + 1 (ldlt.c:367) into dScal_[8 ..],
+// maxbc_r = MAX(maxv(fx_r), maxv(fy_r)) + 1 (ldlt.c:367) into dScal_'s kScMaxbc,
 // read back with the pass's residuals (no copy or wait of its own), and the
 // right-hand sides permuted into dZ_ (k_perm_in2, which also clears the
 // sweep's eps slots and consistency flags).  part: the reduction's partials.
@@ -1471,10 +1464,10 @@ void KktDevice::enqueue_pass_head(int R, double* const* dfy, double* const* dfx,
         J.fx[r] = dfx[r];
         J.z[r] = dZ_.get() + static_cast<size_t>(r) * T_;
     }
-    launch_reduce(j, part, dScal_.get() + 8, s);
-    xsum(dScal_.get() + 8, 2 * R, RedOp::Max);
+    launch_reduce(j, part, dScal_.get() + kScMaxbc, s);
+    xsum(dScal_.get() + kScMaxbc, 2 * R, RedOp::Max);
     hipLaunchKernelGGL(k_perm_in2, dim3(ceil_div(T_, NT), R), dim3(NT), 0, s, T_, m_, dperm_.get(), J, dIncons_.get(),
-                       dScal_.get() + 4);
+                       sweep_eps());
 }
 
 // The forward pre-pass (kkt_device.h PrePass), forked off the object's stream
@@ -1550,17 +1543,23 @@ bool KktDevice::finish_pass(bool fused) {
     IPO_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_min_abs_partial, dim3(kRedBlocks), dim3(NT), 0, s, dDg_.get(), T_, dPart_.get());
     if (xch_) {   // every shard must take the same eps_diag / dependent-pivot / redo decisions
-        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, dPart_.get(), 1, 1u, dFacScal_.get());
-        hipLaunchKernelGGL(k_flag_to_scalar, dim3(1), dim3(1), 0, s, dFlags_.get(), dFacScal_.get() + 1);
-        hipLaunchKernelGGL(k_flag_to_scalar, dim3(1), dim3(1), 0, s, dFlags_.get() + 1, dFacScal_.get() + 2);
-        xsum(dFacScal_.get(), 3, RedOp::Max);
-        hipLaunchKernelGGL(k_pack_ints, dim3(1), dim3(3), 0, s, dFlags_.get(), 3, dFacScal_.get() + 3);
+        static_assert(kFsNegMinD == 0 && kFsNdepMax == 1 && kFsBailMax == 2, "one allreduce over the three");
+        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, dPart_.get(), 1, 1u,
+                           dFacScal_.get() + kFsNegMinD);
+        hipLaunchKernelGGL(k_flag_to_scalar, dim3(1), dim3(1), 0, s, dFlags_.get() + kFlagNdep,
+                           dFacScal_.get() + kFsNdepMax);
+        hipLaunchKernelGGL(k_flag_to_scalar, dim3(1), dim3(1), 0, s, dFlags_.get() + kFlagBail,
+                           dFacScal_.get() + kFsBailMax);
+        xsum(dFacScal_.get(), kFsFlags, RedOp::Max);
+        hipLaunchKernelGGL(k_pack_ints, dim3(1), dim3(kFlagReadWords), 0, s, dFlags_.get(), kFlagReadWords,
+                           dFacScal_.get() + kFsFlags);
     } else {
         // min|d| and the three flags in one read-back, one launch
-        hipLaunchKernelGGL(k_finish_reduce_pack, dim3(1), dim3(kRedThreads), 0, s, dPart_.get(), 1, 1u, dFacScal_.get(),
-                           static_cast<const int*>(dFlags_.get()), 3, dFacScal_.get() + 3);
+        hipLaunchKernelGGL(k_finish_reduce_pack, dim3(1), dim3(kRedThreads), 0, s, dPart_.get(), 1, 1u,
+                           dFacScal_.get() + kFsNegMinD, static_cast<const int*>(dFlags_.get()), kFlagReadWords,
+                           dFacScal_.get() + kFsFlags);
     }
-    IPO_HIP_CHECK(hipMemcpyAsync(hScal_, dFacScal_.get(), 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+    IPO_HIP_CHECK(hipMemcpyAsync(hScal_, dFacScal_.get(), kFsCount * sizeof(double), hipMemcpyDeviceToHost, s));
     if (timing_) IPO_HIP_CHECK(hipEventRecord(ev1_, s));
     IPO_HIP_CHECK(hipStreamSynchronize(s));
     if (gst_n_ > 0) {      // developer stamps of one gather launch (IPO_HIP_GATHER_STAMPS)
@@ -1580,11 +1579,15 @@ bool KktDevice::finish_pass(bool fused) {
         gst_group_ = -1;
     }
     {
-        int f[3];
-        std::memcpy(f, hScal_ + 3, sizeof(f));
-        hFlags_[0] = f[0];
-        hFlags_[1] = f[1];
-        hFlags_[4] = f[2];
+        int f[kFlagReadWords];
+        std::memcpy(f, hScal_ + kFsFlags, sizeof(f));
+        FactorVerdict& v = verdict_;
+        v.min_d = -hScal_[kFsNegMinD];
+        v.ndep = f[kFlagNdep];
+        v.bail = f[kFlagBail];
+        v.tail_block = f[kFlagTailBlock];
+        v.ndep_all = xch_ ? static_cast<int>(hScal_[kFsNdepMax]) : v.ndep;
+        v.bail_all = xch_ ? static_cast<int>(hScal_[kFsBailMax]) : v.bail;
     }
     if (timing_) {
         float ms = 0;
@@ -1592,8 +1595,7 @@ bool KktDevice::finish_pass(bool fused) {
         tm_.factor_ms += ms;
         ph_collect();
     }
-    const bool bail = xch_ ? hScal_[2] > 0 : hFlags_[1] != 0;
-    return !(fused && bail);
+    return !(fused && verdict_.any_bail());
 }
 
 // The dense tail's look-ahead steps [t0, ntb) as one persistent launch
@@ -1603,16 +1605,18 @@ bool KktDevice::finish_pass(bool fused) {
 void KktDevice::launch_tail_from(int t0, bool reset) {
     hipStream_t s = stream_;
     const PlanView pv = plan_view();
-    const size_t ncnt = reset ? drun_cnt_.size() : 1;
-    IPO_HIP_CHECK(hipMemsetAsync(drun_cnt_.get(), 0, ncnt * sizeof(int), s));
+    const RunCounters cnt = run_counters();
+    // every counter (the ticket comes first), or the ticket alone
+    const size_t ncnt = reset ? RunCounters::words(plan_.ntb) : 1;
+    IPO_HIP_CHECK(hipMemsetAsync(cnt.ticket, 0, ncnt * sizeof(int), s));
     TailRun rc;
     rc.items = drun_items_.get() + h_.run_ptr[t0];
     rc.n = h_.run_ptr[plan_.ntb] - h_.run_ptr[t0];
     rc.t0 = t0;
-    rc.ticket = drun_cnt_.get();
-    rc.pdone = drun_cnt_.get() + 1;
-    rc.vseq = drun_cnt_.get() + 1 + plan_.ntb;
-    rc.cdone = run_cdone();
+    rc.ticket = cnt.ticket;
+    rc.pdone = cnt.pdone;
+    rc.vseq = cnt.vseq;
+    rc.cdone = cnt.cdone;
     if (h_.paths.run_winpub) {
         if (run_epoch_ == INT_MAX) {      // (never within a process's life: one epoch per factorisation)
             IPO_HIP_CHECK(hipMemsetAsync(drun_wflag_.get(), 0, drun_wflag_.bytes(), s));
@@ -1620,7 +1624,7 @@ void KktDevice::launch_tail_from(int t0, bool reset) {
         }
         rc.pub = drun_pub_.get();
         rc.wflag = drun_wflag_.get();
-        rc.pread = rc.vseq + static_cast<size_t>(plan_.ntb) * plan_.ntb;
+        rc.pread = cnt.pread;
         // a resumed run: steps >= t0 count their readers afresh
         if (!reset) IPO_HIP_CHECK(hipMemsetAsync(rc.pread + t0, 0, (plan_.ntb - t0) * sizeof(int), s));
         rc.epoch = ++run_epoch_;
@@ -1660,12 +1664,13 @@ void KktDevice::repair_tail() {
     hipStream_t s = stream_;
     const PlanView pv = plan_view();
     for (;;) {
-        const int tb = hFlags_[4] - 1;
+        const int tb = verdict_.tail_col();
         tm_.tail_repairs++;
         if (timing_) IPO_HIP_CHECK(hipEventRecord(ev0_, s));
-        IPO_HIP_CHECK(hipMemsetAsync(dFlags_.get() + 1, 0, 2 * sizeof(int), s));
+        static_assert(kFlagTailBlock == kFlagBail + 1, "one memset clears both");
+        IPO_HIP_CHECK(hipMemsetAsync(dFlags_.get() + kFlagBail, 0, 2 * sizeof(int), s));
         TailView tv = tail_view();
-        if (hFlags_[1] & 16) launch_tail_restore(pv, tv, tb, s);   // other workgroups of the DEP pass wrote
+        if (verdict_.needs_restore()) launch_tail_restore(pv, tv, tb, s);   // other workgroups of the DEP pass wrote
         ph_begin(s);
         if (tb > 0) launch_tail_colupdate(pv, tv, tb - 1, s);
         ph_end(kPhTail, tb > 0, s);
@@ -1682,11 +1687,11 @@ void KktDevice::repair_tail() {
             for (int b = 0; b < kDepBatch; b++)
                 launch_tail_dep_round(pv, tv, tb, r + b, dDepSt_.get(), dDepI_.get(), s);
             ph_end(kPhTail, kDepBatch, s);
-            IPO_HIP_CHECK(hipMemcpyAsync(hFlags_ + 6, dDepI_.get() + 4 * ((r + kDepBatch) & 1) + 2, sizeof(int),
+            IPO_HIP_CHECK(hipMemcpyAsync(hDepDone_, dDepI_.get() + 4 * ((r + kDepBatch) & 1) + 2, sizeof(int),
                                          hipMemcpyDeviceToHost, s));
             IPO_HIP_CHECK(hipStreamSynchronize(s));
             tm_.tail_dep_rounds += kDepBatch;
-            if (hFlags_[6]) break;
+            if (*hDepDone_) break;
         }
         if (h_.paths.tail_run) {
             launch_tail_from(tb + 1, false);
@@ -1696,7 +1701,7 @@ void KktDevice::repair_tail() {
             ph_end(kPhTail, plan_.ntb - tb - 1, s);
         }
         if (finish_pass(true)) break;
-        if ((hFlags_[1] & ~16) != 4 || hFlags_[4] - 1 <= tb)   // cannot happen: a later tail column or nothing
+        if (!verdict_.tail_only() || verdict_.tail_col() <= tb)   // cannot happen: a later tail column or nothing
             throw std::runtime_error("kkt: dense-tail repair did not advance");
     }
 }
@@ -1836,7 +1841,7 @@ void KktDevice::solve_multi(int R, const double* dE, const double* dD, double* c
                     na++;
                 }
             hipLaunchKernelGGL(k_perm_in2, dim3(ceil_div(T, NT), na), dim3(NT), 0, s, T, m, dperm_.get(), J,
-                               dIncons_.get(), dScal_.get() + 4);
+                               dIncons_.get(), sweep_eps());
         }
         eps_cleared_ = true;
         // (the pre-pass ran the tail lead too: IPO_HIP_LEAD_TRAIL)
@@ -1878,27 +1883,31 @@ void KktDevice::solve_multi(int R, const double* dE, const double* dD, double* c
         // residuals and the consistency flags in one read-back
         if (xch_) {
             hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, dPart_.get(), nq, (1u << nq) - 1u,
-                               dScal_.get());
-            xsum(dScal_.get(), nq, RedOp::Max);
-            hipLaunchKernelGGL(k_pack_ints, dim3(1), dim3(2), 0, s, dIncons_.get(), 2, dScal_.get() + 6);
+                               dScal_.get() + kScRes);
+            xsum(dScal_.get() + kScRes, nq, RedOp::Max);
+            hipLaunchKernelGGL(k_pack_ints, dim3(1), dim3(2), 0, s, dIncons_.get(), 2, dScal_.get() + kScIncons);
         } else {
             hipLaunchKernelGGL(k_finish_reduce_pack, dim3(1), dim3(kRedThreads), 0, s, dPart_.get(), nq,
-                               (1u << nq) - 1u, dScal_.get(), static_cast<const int*>(dIncons_.get()), 2,
-                               dScal_.get() + 6);
+                               (1u << nq) - 1u, dScal_.get() + kScRes, static_cast<const int*>(dIncons_.get()), 2,
+                               dScal_.get() + kScIncons);
         }
-        IPO_HIP_CHECK(hipMemcpyAsync(hScal_, dScal_.get(), (pass[0] + pass[1] == 0 ? 8 + 2 * R : 7) * sizeof(double),
+        IPO_HIP_CHECK(hipMemcpyAsync(hScal_, dScal_.get(), (first ? kScMaxbc + 2 * R : kScReadLater) * sizeof(double),
                                      hipMemcpyDeviceToHost, s));
         IPO_HIP_CHECK(hipStreamSynchronize(s));
-        if (pass[0] + pass[1] == 0)
-            for (int r = 0; r < R; r++)
-                maxbc[r] = (hScal_[8 + 2 * r] > hScal_[8 + 2 * r + 1] ? hScal_[8 + 2 * r] : hScal_[8 + 2 * r + 1]) + 1;
-        std::memcpy(hFlags_ + 2, hScal_ + 6, 2 * sizeof(int));
+        if (first)
+            for (int r = 0; r < R; r++) {
+                const double* mb = hScal_ + kScMaxbc + 2 * r;
+                maxbc[r] = (mb[0] > mb[1] ? mb[0] : mb[1]) + 1;
+            }
+        int slot_incons[2];      // of the sweep's right-hand-side slots
+        std::memcpy(slot_incons, hScal_ + kScIncons, sizeof(slot_incons));
+        const double* res = hScal_ + kScRes;
         int q = 0;
         for (int r = 0; r < R; r++) {
             if (!active[r]) continue;
-            incons[r] = hFlags_[2 + q];
+            incons[r] = slot_incons[q];
             rs_old[r] = rs[r];
-            rs[r] = hScal_[q++];
+            rs[r] = res[q++];
             pass[r]++;
             active[r] = rs[r] > 1.0e-10 * maxbc[r] && rs[r] < rs_old[r] / 2;
         }

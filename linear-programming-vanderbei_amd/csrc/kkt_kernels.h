@@ -38,7 +38,7 @@ struct PlanView {
     double* Lx;
     double* dg;
     int* live;
-    int* flags;      // [0] dependent pivots, [1] fused panel kernel bail-out, [2] 1 + bailed tail block
+    int* flags;      // [kFlagWords]: kFlagNdep, kFlagBail, kFlagTailBlock, kFlagSpecNdep (kkt_flags.h)
     const int* sign; // node class per new index: -1 y-node, +1 x-node
     double* dscale;  // sum of |terms| that formed each pivot (zero-pivot test)
     double tau;      // pivot d is "zero" when |d| <= tau * dscale
@@ -120,7 +120,7 @@ void launch_trsm(const PlanView& pv, int u0, int count, const TailView& tv, int 
 // Fused diagonal block + panel rows (the fast path of launch_diag +
 // launch_trsm): fused units [f0, f0+count) of a sparse level, or, with
 // fu_sup == nullptr, block column kb of the dense tail.  A pivot that fails
-// the zero test sets flags[1] and leaves the panel unwritten.
+// the zero test sets its kBail* bit of flags[kFlagBail] and leaves the panel unwritten.
 void launch_panel(const PlanView& pv, const int* fu_sup, const int* fu_j, int f0, int count, const TailView& tv,
                   int kb, hipStream_t s);
 // Look-ahead dense tail (fused path with k_panel_w): step t = panel of block

@@ -275,9 +275,9 @@ struct KktKnobs {
         k.sf = flag("IPO_HIP_SF", true);
         k.overlap = flag("IPO_HIP_OVERLAP", true);
         k.prepass = flag("IPO_HIP_PREPASS", true);
-    k.lead_trail = num("IPO_HIP_LEAD_TRAIL", -1);
-    if (k.lead_trail < 0 || k.lead_trail > 2) k.lead_trail = -1;
-    k.lead_helpers = std::max(1, num("IPO_HIP_LEAD_HELPERS", kTrailHelpers));
+        k.lead_trail = num("IPO_HIP_LEAD_TRAIL", -1);
+        if (k.lead_trail < 0 || k.lead_trail > 2) k.lead_trail = -1;
+        k.lead_helpers = std::max(1, num("IPO_HIP_LEAD_HELPERS", kTrailHelpers));
         k.chain_lead = flag("IPO_HIP_CHAIN_LEAD", true);
         k.chain_pairs = flag("IPO_HIP_CHAIN_PAIRS", false);
         k.tail_run = flag("IPO_HIP_TAIL_RUN", true);

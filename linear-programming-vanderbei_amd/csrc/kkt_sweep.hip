@@ -1369,13 +1369,13 @@ __device__ __forceinline__ void lds_sync() {     // LDS-only barrier: global sto
 //   (a) a poll of cdone[c] (col_wait),
 //   (b) a helper's wait for the lead's z granules (gran_wait_bail),
 //   (c) the lead's wait for a helper's partial (the loop in step()),
-// and each of them also reads the run's bail word p.flags[2] on every trip
-// and gives up when it is non-zero.  k_tail_run ends short of completing a
-// column only through a panel that bails, which raises flags[2] before it
-// posts (panel_w_body: the zero test of a first pass, and a DEP pass's
-// contradicted speculation, flags[1] bit 16, alike), or through items that
-// skip themselves because they read flags[2] set (run_wait, pre_wait): so
-// either every counter completes or flags[2] becomes and stays non-zero
+// and each of them also reads the run's bail word p.flags[kFlagTailBlock] on
+// every trip and gives up when it is non-zero.  k_tail_run ends short of
+// completing a column only through a panel that bails, which raises the bail
+// word before it posts (panel_w_body: the zero test of a first pass, and a DEP pass's
+// contradicted speculation, kBailRestore, alike), or through items that
+// skip themselves because they read the bail word set (run_wait, pre_wait): so
+// either every counter completes or the bail word becomes and stays non-zero
 // while this launch lives (the host clears it only after both streams are at
 // rest).  With the counters complete, (b) and (c) are the other form's
 // waits: ticket k's block is held by a running workgroup once tickets < k
@@ -1385,7 +1385,7 @@ __device__ __forceinline__ void lds_sync() {     // LDS-only barrier: global sto
 // workgroup's abort word in LDS and goes on to the next barrier B; every
 // wave reads the word after each B and returns there, so no wave is left at
 // a barrier and no workgroup waits for a granule of one that left -- its
-// own polls read flags[2] too.  An aborted launch's z, granules and partials
+// own polls read the bail word too.  An aborted launch's z, granules and partials
 // are incomplete; the factorisation it trailed has bailed, so its pre-pass
 // is dropped and the normal pass rewrites them (a later epoch).
 #ifndef IPO_TRAIL_SLEEP
@@ -1446,7 +1446,7 @@ k_tail_fwd_lead(PlanView p, TailView tv, SweepVecs V, const double* __restrict__
     extern __shared__ double lds[];
     constexpr int K = kLeadBlocks;
     const int nt = tv.nt, tc = tv.tc, ntb = tv.ntb;
-    const int* bailp = p.flags + 2;
+    const int* bailp = p.flags + kFlagTailBlock;
     int* const abort_p = reinterpret_cast<int*>(lds + 2 * PC * (PC + 1) + K * 2 * PC + 2 * 4 * 64) + 2 * PC;
     // waves: 0 solves (right-hand side 0; 6, on SIMD 2, solves 1 when R = 2:
     // two independent chains at one wave each); 1, 2, 3 and 5 are column
@@ -2452,7 +2452,7 @@ int KktDevice::run_sweep_steps(const std::vector<SweepStep>& steps, bool forward
             const int tb = static_cast<int>(lead_ticket_next_);
             lead_ticket_next_ += grid;
             hipLaunchKernelGGL(k_tail_fwd_lead<R>, dim3(grid), dim3(kLeadNT), kChainLds, s, pv, tv, V, epsp,
-                               dChainGran_.get(), dChainGran_.get() + static_cast<size_t>(plan_.ntb) * 2 * 128,
+                               dChainGran_.get(), dChainGran_.get() + ChainGran::part_at(plan_.ntb),
                                ++chain_epoch_, dlead_ticket_.get(), tb, static_cast<const int*>(nullptr));
 #ifdef IPO_LEAD_STAMPS
             if (chain_epoch_ % 64 == 41) {
@@ -2507,7 +2507,7 @@ int KktDevice::run_sweep_steps(const std::vector<SweepStep>& steps, bool forward
 // The forward pre-pass's share of the forward list (kkt_device.h PrePass):
 // steps [0, split) for the R right-hand sides in dZ_, on q.
 void KktDevice::run_prepass_steps(int R, hipStream_t q) {
-    double* epsp = dScal_.get() + 4;
+    double* epsp = sweep_eps();
     const size_t split = static_cast<size_t>(h_.sweep.split);
     if (R == 2) run_sweep_steps<2>(h_.sweep.fwd, true, dZ_.get(), epsp, 0, split, q);
     else run_sweep_steps<1>(h_.sweep.fwd, true, dZ_.get(), epsp, 0, split, q);
@@ -2519,23 +2519,23 @@ void KktDevice::run_prepass_steps(int R, hipStream_t q) {
 // as the other form, or beside it on the pre-pass's stream, with at most
 // knobs_.lead_helpers helper workgroups that take the blocks by ticket, so
 // that few CUs hold a poller's LDS while the run's visits want them.  Its
-// ticket follows TailRun::cdone in drun_cnt_ (zeroed with the run's counters).
+// ticket is RunCounters::lead_ticket (zeroed with the run's counters).
 void KktDevice::launch_lead_trail(int R, hipStream_t s, bool beside) {
     const PlanView pv = plan_view();
     const TailView tv = tail_view();
     const SweepVecs V{dZ_.get(), static_cast<size_t>(T_), dYbuf_.get(), h_.ybuf_stride};
     const int nhb = std::max(0, plan_.ntb - 1 - kLeadBlocks);
     const int grid = 1 + (beside ? std::min(nhb, knobs_.lead_helpers) : nhb);
-    const double* epsp = dScal_.get() + 4;
+    const double* epsp = sweep_eps();
     gran_t* gran = dChainGran_.get();
-    gran_t* pgran = gran + static_cast<size_t>(plan_.ntb) * 2 * 128;
-    int* cdone = run_cdone();
+    gran_t* pgran = gran + ChainGran::part_at(plan_.ntb);
+    const RunCounters cnt = run_counters();
     if (R == 2)
         hipLaunchKernelGGL((k_tail_fwd_lead<2, true>), dim3(grid), dim3(kLeadNT), kLeadTrailLds, s, pv, tv, V, epsp, gran,
-                           pgran, ++chain_epoch_, cdone + plan_.ntb, 0, static_cast<const int*>(cdone));
+                           pgran, ++chain_epoch_, cnt.lead_ticket, 0, static_cast<const int*>(cnt.cdone));
     else
         hipLaunchKernelGGL((k_tail_fwd_lead<1, true>), dim3(grid), dim3(kLeadNT), kLeadTrailLds, s, pv, tv, V, epsp, gran,
-                           pgran, ++chain_epoch_, cdone + plan_.ntb, 0, static_cast<const int*>(cdone));
+                           pgran, ++chain_epoch_, cnt.lead_ticket, 0, static_cast<const int*>(cnt.cdone));
 }
 
 // Ticket base of the next sync-free launch of direction d over nitems items:
@@ -2566,7 +2566,7 @@ void KktDevice::tail_rhs_end(double* dz, int R) {
 // rawsolve (ldlt.c:433-505) of R right-hand sides at dz + r * K, in place.
 void KktDevice::rawsolve(double* dz, int R, size_t fwd_first) {
     hipStream_t s = stream_;
-    double* epsp = dScal_.get() + 4;        // eps of right-hand side r at epsp[r]
+    double* epsp = sweep_eps();             // eps of right-hand side r at epsp[r]
     if (ndep_ > 0) {
         // eps = epssol * max|z[0..n)| (ldlt.c:446: first n entries of the permuted vector)
         RedJobs j{};

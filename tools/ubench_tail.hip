@@ -37,7 +37,7 @@ int main(int argc, char** argv) {
     const size_t bytes = (size_t)nt * nt * sizeof(double);
     CK(hipMalloc(&dS, bytes)); CK(hipMalloc(&dS0, bytes)); CK(hipMalloc(&dW, (size_t)ntb * nt * 64 * 8));
     CK(hipMalloc(&ddg, nt * 8)); CK(hipMalloc(&ddsc, nt * 8)); CK(hipMalloc(&ddsc0, nt * 8));
-    CK(hipMalloc(&dlive, nt * 4)); CK(hipMalloc(&dflags, 16)); CK(hipMalloc(&dsign, nt * 4));
+    CK(hipMalloc(&dlive, nt * 4)); CK(hipMalloc(&dflags, ipo::kFlagWords * sizeof(int))); CK(hipMalloc(&dsign, nt * 4));
     CK(hipMemcpy(dS0, S.data(), bytes, hipMemcpyHostToDevice));
     CK(hipMemcpy(ddsc0, dsc.data(), nt * 8, hipMemcpyHostToDevice));
     CK(hipMemcpy(dsign, sign.data(), nt * 4, hipMemcpyHostToDevice));
@@ -71,7 +71,7 @@ int main(int argc, char** argv) {
     std::vector<int> rptr;
     uint2* ditems = nullptr;
     int* dcnt = nullptr;
-    const size_t ncnt = 1 + ntb + (size_t)ntb * ntb + ntb;   // ticket, pdone[ntb], vseq[ntb * ntb], pread[ntb]
+    const size_t ncnt = ipo::RunCounters::words(ntb);   // (cdone and the lead's ticket stay unused: no trailing lead here)
     int cus_run = 0;
     if (run) {
         CK(hipDeviceGetAttribute(&cus_run, hipDeviceAttributeMultiprocessorCount, 0));
@@ -105,13 +105,14 @@ int main(int argc, char** argv) {
         rc.items = ditems;
         rc.n = rptr[ntb];
         rc.t0 = 0;
-        rc.ticket = dcnt;
-        rc.pdone = dcnt + 1;
-        rc.vseq = dcnt + 1 + ntb;
+        const ipo::RunCounters cnt(dcnt, ntb);
+        rc.ticket = cnt.ticket;
+        rc.pdone = cnt.pdone;
+        rc.vseq = cnt.vseq;
         if (dwpub) {          // the window hand-off (UB_WINPUB=0: off), as the library's default
             rc.pub = dwpub;
             rc.wflag = dwflag;
-            rc.pread = dcnt + 1 + ntb + ntb * ntb;
+            rc.pread = cnt.pread;
             rc.epoch = ++wepoch;
         }
         rc.trace = dtrace;
@@ -121,7 +122,7 @@ int main(int argc, char** argv) {
     if (run) {      // the per-step launches' pivots and factor, for the comparison
         CK(hipMemcpy(dS, dS0, bytes, hipMemcpyDeviceToDevice));
         CK(hipMemcpy(ddsc, ddsc0, nt * 8, hipMemcpyDeviceToDevice));
-        CK(hipMemset(dflags, 0, 16));
+        CK(hipMemset(dflags, 0, ipo::kFlagWords * sizeof(int)));
         for (int t = 0; t < ntb; t++) ipo::launch_tail_step(pv, tv, t, 0);
         CK(hipDeviceSynchronize());
         g_step.resize(nt);
@@ -135,7 +136,7 @@ int main(int argc, char** argv) {
     for (int r = 0; r < reps + 1; r++) {
         CK(hipMemcpy(dS, dS0, bytes, hipMemcpyDeviceToDevice));
         CK(hipMemcpy(ddsc, ddsc0, nt * 8, hipMemcpyDeviceToDevice));
-        CK(hipMemset(dflags, 0, 16));
+        CK(hipMemset(dflags, 0, ipo::kFlagWords * sizeof(int)));
         CK(hipDeviceSynchronize());
         CK(hipEventRecord(ev[0], 0));
         if (run) {
@@ -157,12 +158,12 @@ int main(int argc, char** argv) {
             step_us[t] += 1e3 * ms;
         }
     }
-    int fl[4];
-    CK(hipMemcpy(fl, dflags, 16, hipMemcpyDeviceToHost));
+    int fl[ipo::kFlagWords];
+    CK(hipMemcpy(fl, dflags, sizeof(fl), hipMemcpyDeviceToHost));
     const double flops = (double)nt * nt * nt / 3.0;
     std::printf("visit chunk %d; ", tv.vk);
     std::printf("nt %d (%d block columns): %.3f ms per factor, %.2f TFLOP/s of nt^3/3, bail flags %d %d %d\n", nt, ntb,
-                total / reps, flops / (total / reps * 1e-3) / 1e12, fl[0], fl[1], fl[2]);
+                total / reps, flops / (total / reps * 1e-3) / 1e12, fl[ipo::kFlagNdep], fl[ipo::kFlagBail], fl[ipo::kFlagTailBlock]);
     std::printf("per step (us):");
     for (int t = 0; t < ntb; t++) std::printf("%s%.1f", t % 16 ? " " : "\n  ", step_us[t] / reps);
     std::printf("\n");
@@ -212,7 +213,7 @@ int main(int argc, char** argv) {
     // one more run up to the stamped step, so the stamps are that step's
     CK(hipMemcpy(dS, dS0, bytes, hipMemcpyDeviceToDevice));
     CK(hipMemcpy(ddsc, ddsc0, nt * 8, hipMemcpyDeviceToDevice));
-    CK(hipMemset(dflags, 0, 16));
+    CK(hipMemset(dflags, 0, ipo::kFlagWords * sizeof(int)));
     for (int t = 0; t <= stamp_step; t++) ipo::launch_tail_step(pv, tv, t, 0);
     CK(hipDeviceSynchronize());
     long long st[8][16];
