@@ -20,7 +20,8 @@ extern "C" {
 /* ---- METHOD plug-in ------------------------------------------------------
  * Replaces solver() of src/ipo/hsd.c:27-29 (default, like makefile:57),
  * src/ipo/intpt.c:33-35 (set IPO_HIP_METHOD=intpt) and src/ipo/hsdls.c:38-40
- * (IPO_HIP_METHOD=hsdls); prototype from
+ * (IPO_HIP_METHOD=hsdls); IPO_HIP_METHOD=pc: the predictor-corrector
+ * extension below (method 4), with intpt's banner and trace; prototype from
  * src/common/solve.c:24-26.  Solves  max c'x + f  s.t.  Ax <= b, x >= 0,
  * A m x n CSC (kA[n+1], iA[nz], A[nz]), 0-based.  x, z: n; y, w: m (the
  * caller may allocate more, as solve.c:194-197 does).  Prints the banner
@@ -92,9 +93,17 @@ typedef struct {
     long   tail_dep_rounds;  /* k_tail_dep launches of those repairs                  */
 } ipo_hip_stats;
 
-/* method: 0 = hsd, 1 = intpt, 2 = hsdls (3 = qp: with an empty Q, see
+/* method: 0 = hsd, 1 = intpt, 2 = hsdls, 4 = pc (3 = qp: with an empty Q, see
  * ipo_hip_solve_qp).  trace may be NULL (silent).  timing != 0 records
- * per-phase HIP-event times. */
+ * per-phase HIP-event times.
+ * Method 4, "pc" (an extension: not in the reference) is
+ * Mehrotra's predictor-corrector on intpt's start point, printed line, stop
+ * rule and status codes: one factorisation and two refined solves an
+ * iteration (an affine predictor, a centring parameter from its outcome, a
+ * corrected direction), one step length min(1, 0.95 / largest ratio) for
+ * x, z, y, w.  It gives up (2 / 4) when a residual norm grows tenfold in
+ * one iteration while above 1e-6 (1 + its value on line 0).  Default
+ * iteration limit 200. */
 int ipo_hip_solve(int method, int m, int n, int nz, const int *iA, const int *kA, const double *A,
                   const double *b, const double *c, double f, double *x, double *y, double *w, double *z,
                   FILE *trace, int max_iter, int timing, ipo_hip_stats *stats);
@@ -131,11 +140,19 @@ int ipo_hip_solve_qp(int m, int n, int nz, const int *iA, const int *kA, const d
                      const double *c, double f, const int *kQ, const int *iQ, const double *Q, double *x,
                      double *y, double *w, double *z, FILE *trace, int max_iter, int timing,
                      ipo_hip_stats *stats);
+/* ipo_hip_solve_qp by method 3 (qp: ipo_hip_solve_qp itself) or 4 (pc, the
+ * predictor-corrector of ipo_hip_solve with D + Q on the x block); any other
+ * method returns 7 with an error text before a device is touched. */
+int ipo_hip_solve_qp_ex(int method, int m, int n, int nz, const int *iA, const int *kA, const double *A,
+                        const double *b, const double *c, double f, const int *kQ, const int *iQ,
+                        const double *Q, double *x, double *y, double *w, double *z, FILE *trace,
+                        int max_iter, int timing, ipo_hip_stats *stats);
 /* A persistent context with Q: with a nonempty Q it runs with
- * ipo_hip_ctx_run(ctx, 3, ...) only (methods 0-2 return 7 with an error
- * text); _download / _destroy as usual.  Method 3 on a context without Q
- * (ipo_hip_ctx_create, or an empty Q here) runs with an empty Q: the LP, by
- * method 1's iteration; on a sharded context it returns 7.  NULL on error
+ * ipo_hip_ctx_run(ctx, 3, ...) and (ctx, 4, ...) only (methods 0-2 return 7
+ * with an error text); _download / _destroy as usual.  Method 3 on a context
+ * without Q (ipo_hip_ctx_create, or an empty Q here) runs with an empty Q:
+ * the LP, by method 1's iteration, and method 4 runs the LP on the LP's
+ * factor; on a sharded context both return 7.  NULL on error
  * (ipo_hip_last_error). */
 ipo_hip_ctx *ipo_hip_ctx_create_qp(int m, int n, const int *kA, const int *iA, const double *A,
                                    const double *b, const double *c, double f, const int *kQ, const int *iQ,
@@ -181,7 +198,10 @@ int ipo_hip_run_mps(const char *path, int method, FILE *out, int timing, ipo_hip
  * it, hsd.c:290-291).
  * method 3 (qp) solves the file's QP, QUADS included (ipo_hip_mps_load_qp;
  * methods 0-2 ignore QUADS, as solvelp does); with IPO_HIP_SPLIT_FREE it is
- * refused: 7 and an error text, nothing solved. */
+ * refused: 7 and an error text, nothing solved.  Method 4 (pc) takes the
+ * same transform, QUADS included (a file without QUADS is the LP, on the
+ * LP's factor); with IPO_HIP_SPLIT_FREE it takes the LP transform of a file
+ * without QUADS and is refused like method 3 on a file with QUADS. */
 #define IPO_HIP_SPLIT_FREE 1
 int ipo_hip_run_mps_ex(const char *path, int method, int flags, const char *solfile, FILE *out, int timing,
                        ipo_hip_stats *stats);

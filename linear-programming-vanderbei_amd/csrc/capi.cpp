@@ -33,14 +33,19 @@ ipo::Method method_from_env() {
     const char* e = std::getenv("IPO_HIP_METHOD");
     if (e && !std::strcmp(e, "intpt")) return ipo::Method::Intpt;
     if (e && !std::strcmp(e, "hsdls")) return ipo::Method::Hsdls;
+    if (e && !std::strcmp(e, "pc")) return ipo::Method::Pc;
     return ipo::Method::Hsd;
 }
 
 ipo::Method method_from_int(int m) {
-    return m == 1 ? ipo::Method::Intpt : m == 2 ? ipo::Method::Hsdls : m == 3 ? ipo::Method::Qp : ipo::Method::Hsd;
+    return m == 1   ? ipo::Method::Intpt
+           : m == 2 ? ipo::Method::Hsdls
+           : m == 3 ? ipo::Method::Qp
+           : m == 4 ? ipo::Method::Pc
+                    : ipo::Method::Hsd;
 }
 
-// MAX_ITER of each method: hsd.c:25, intpt.c:31, hsdls.c:25
+// MAX_ITER of each method: hsd.c:25, intpt.c:31, hsdls.c:25 (qp and pc: intpt's)
 int default_max_iter(ipo::Method m) { return m == ipo::Method::Hsdls ? 600 : 200; }
 
 // hsd.c:70-92 / intpt.c:70-92: tiny problems are echoed before the banner
@@ -222,10 +227,22 @@ int ipo_hip_solve(int method, int m, int n, int nz, const int* iA, const int* kA
 int ipo_hip_solve_qp(int m, int n, int nz, const int* iA, const int* kA, const double* A, const double* b,
                      const double* c, double f, const int* kQ, const int* iQ, const double* Q, double* x, double* y,
                      double* w, double* z, FILE* trace, int max_iter, int timing, ipo_hip_stats* stats) {
+    return ipo_hip_solve_qp_ex(3, m, n, nz, iA, kA, A, b, c, f, kQ, iQ, Q, x, y, w, z, trace, max_iter, timing, stats);
+}
+
+int ipo_hip_solve_qp_ex(int method, int m, int n, int nz, const int* iA, const int* kA, const double* A,
+                        const double* b, const double* c, double f, const int* kQ, const int* iQ, const double* Q,
+                        double* x, double* y, double* w, double* z, FILE* trace, int max_iter, int timing,
+                        ipo_hip_stats* stats) {
+    if (method != 3 && method != 4) {
+        set_err("ipo_hip_solve_qp_ex: method " + std::to_string(method) + " takes no Q (3 = qp and 4 = pc do)");
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return 7;
+    }
     ipo::QBlock qb;
     qb.kQ = kQ; qb.iQ = iQ; qb.Q = Q;
-    return solve_impl(ipo::Method::Qp, m, n, nz, iA, kA, A, b, c, f, x, y, w, z, trace, max_iter, timing, stats, nullptr,
-                      &qb);
+    return solve_impl(method_from_int(method), m, n, nz, iA, kA, A, b, c, f, x, y, w, z, trace, max_iter, timing, stats,
+                      nullptr, &qb);
 }
 
 ipo_hip_ctx* ipo_hip_ctx_create_qp(int m, int n, const int* kA, const int* iA, const double* A, const double* b,
@@ -340,18 +357,23 @@ int ipo_hip_run_mps(const char* path, int method, FILE* out, int timing, ipo_hip
 }
 
 namespace {
+constexpr int kSplitWithQuads = 1000;   // load_form: QUADS in a file whose free columns were to be split
 // read + (optionally) split free columns + normalise; returns the
-// to_solver_form status (3: a free variable and no split requested)
+// to_solver_form status (3: a free variable and no split requested).
+// qs: the file's QUADS carried along (methods qp and pc); with the split
+// that is kSplitWithQuads for a file that has QUADS (the split would need
+// Q's rows and columns split with it: not built), the LP for one without
 int load_form(const char* path, int flags, ipo::MpsProblem& p, ipo::MpsProblem& q, ipo::FreeMap& fm,
               ipo::SolverForm& s, std::string& err, FILE* out, ipo::QpBlock* qs = nullptr) {
     const int rc = ipo::read_mps(path, p, &err);
     if (rc) return -rc;
+    if (qs && (flags & IPO_HIP_SPLIT_FREE) && !p.kQ.empty() && p.kQ.back() > 0) return kSplitWithQuads;
     if (out) std::fprintf(out, "m = %d,n = %d,nz = %d \n", p.m, p.n, p.kA.empty() ? 0 : p.kA[p.n]);
     if (flags & IPO_HIP_SPLIT_FREE) {
         ipo::split_free_columns(p, q, fm);
         return ipo::to_solver_form(q, s);
     }
-    if (qs) return ipo::to_solver_form_qp(p, s, *qs);     // method qp: the file's QUADS carried along
+    if (qs) return ipo::to_solver_form_qp(p, s, *qs);
     return ipo::to_solver_form(p, s);
 }
 }  // namespace
@@ -371,15 +393,17 @@ int ipo_hip_run_mps_ex(const char* path, int method, int flags, const char* solf
     ipo::SolverForm s;
     ipo::QpBlock qs;
     std::string err;
-    const bool qp = method == 3;
-    if (qp && (flags & IPO_HIP_SPLIT_FREE)) {
-        // the split would need Q's rows and columns split with it: not built
-        set_err("method qp with IPO_HIP_SPLIT_FREE (split free columns) is not supported");
+    const bool qp = method == 3 || method == 4;      // the methods that take the file's QUADS
+    const auto refuse_split = [&](const char* what) {
+        set_err(std::string("method ") + what + " with IPO_HIP_SPLIT_FREE (split free columns) is not supported");
         if (out) std::fprintf(out, "ERROR: %s\n\n", g_err.c_str());
         if (stats) std::memset(stats, 0, sizeof(*stats));
         return 7;
-    }
+    };
+    // the split would need Q's rows and columns split with it: not built
+    if (method == 3 && (flags & IPO_HIP_SPLIT_FREE)) return refuse_split("qp");
     int status = load_form(path, flags, p, q, fm, s, err, out, qp ? &qs : nullptr);
+    if (status == kSplitWithQuads) return refuse_split("pc on a file with QUADS");
     if (status < 0) {
         set_err(err);
         if (out) std::fprintf(out, "ERROR(%d): %s\n\n", -status, err.c_str());
@@ -404,10 +428,11 @@ int ipo_hip_run_mps_ex(const char* path, int method, int flags, const char* solf
             std::fprintf(out, "\n");
         }
         ipo::QBlock qb;
-        if (qp) { qb.kQ = qs.kQ.data(); qb.iQ = qs.iQ.data(); qb.Q = qs.Q.data(); }
+        const bool withq = qp && !qs.kQ.empty();      // pc after the split: the LP
+        if (withq) { qb.kQ = qs.kQ.data(); qb.iQ = qs.iQ.data(); qb.Q = qs.Q.data(); }
         status = solve_impl(method_from_int(method), s.m, s.n, s.nz, s.iA.data(),
                             s.kA.data(), s.A.data(), s.b.data(), s.c.data(), s.f, x.data(), y.data(), w.data(),
-                            z.data(), out, 0, timing, stats, &dev_err, qp ? &qb : nullptr);   // 0: the method's MAX_ITER
+                            z.data(), out, 0, timing, stats, &dev_err, withq ? &qb : nullptr);   // 0: the method's MAX_ITER
     }
     // a device / host exception is not a numerical outcome: no status text for it
     if (out) {

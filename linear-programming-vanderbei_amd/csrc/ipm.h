@@ -5,6 +5,9 @@
 //   Method::Hsdls  homogeneous self-dual long step,          src/ipo/hsdls.c:38-296
 //   Method::Qp     intpt.c's path following with a quadratic objective term
 //                  (an extension: the reference has no QP loop)
+//   Method::Pc     Mehrotra's predictor-corrector on the same problems, LPs
+//                  and convex QPs: one factorisation and two refined solves
+//                  an iteration (an extension)
 //
 // The host keeps the handful of scalars the reference keeps (phi, psi, mu,
 // theta, ...) and prints the reference's per-iteration trace; every O(m+n)
@@ -22,7 +25,7 @@
 
 namespace ipo {
 
-enum class Method { Hsd = 0, Intpt = 1, Hsdls = 2, Qp = 3 };
+enum class Method { Hsd = 0, Intpt = 1, Hsdls = 2, Qp = 3, Pc = 4 };
 
 struct IpmOptions {
     Method method = Method::Hsd;
@@ -71,7 +74,11 @@ constexpr int kIsNorm2 = 8;     // [2] squared norms of the primal and the dual 
 constexpr int kIsTheta = 11;    // the step length k_step reads (k_hsd_theta)
 constexpr int kIsDphi = 12;     // [2] dphi, dpsi (k_hsd_dphi) for k_hsd_directions and k_hsd_theta
 constexpr int kIsPhiNext = 14;  // [2] the next iteration's phi, psi (k_hsd_theta)
-constexpr int kIsCount = 16;
+// run_pc (none of them is read back by the host):
+constexpr int kIsPcRatio = 16;  // the predictor's largest ratio t (k_pc_affine)
+constexpr int kIsPcDots = 17;   // [6] z'dxa, x'dza, w'dya, y'dwa, dxa'dza, dya'dwa (g1 and g2's terms)
+constexpr int kIsPcMu = 23;     // the centring mu k_pc_rhs and k_pc_directions read (k_pc_mu)
+constexpr int kIsCount = 24;
 
 // Problem uploaded to HBM once; run() iterates from the reference's start
 // point and can be called repeatedly (the bench times run()).
@@ -83,13 +90,14 @@ class IpmSolver {
   public:
     // q: the QP's Q (n x n, full symmetric CSC, positive semidefinite; its
     // qmax is not read): max c'x + f - x'Qx / 2.  With a nonempty Q the
-    // solver runs Method::Qp only, and cannot be sharded.
+    // solver runs Method::Qp and Method::Pc only, and cannot be sharded.
     IpmSolver(int m, int n, const int* kA, const int* iA, const double* A, const double* b, const double* c,
               double f, hipStream_t stream = nullptr, const ShardSpec* shard = nullptr, const QBlock* q = nullptr);
     ~IpmSolver();
     // Throws for an LP method on a solver built with a nonempty Q and for
-    // Method::Qp on a sharded solver.  Method::Qp without Q is the QP with an
-    // empty Q: the LP, on the LP's factor.
+    // Method::Qp or Method::Pc on a sharded solver.  Method::Qp without Q is
+    // the QP with an empty Q: the LP, on the LP's factor.  Method::Pc runs on
+    // solvers with and without Q.
     int run(const IpmOptions& opt, IpmResult* res);
     // copy x (n), y (m), w (m), z (n) of the last run to the host
     void download(double* x, double* y, double* w, double* z) const;
@@ -101,6 +109,8 @@ class IpmSolver {
     int run_intpt(const IpmOptions& opt, IpmResult* res);
     int run_hsdls(const IpmOptions& opt, IpmResult* res);
     int run_qp(const IpmOptions& opt, IpmResult* res);
+    template <bool SW>
+    int run_pc(const IpmOptions& opt, IpmResult* res);   // SW: the swapped factor of a solver with Q
     void reduce(const struct RedJobs& j, int nout);
     // sharded solve: linking-row products A_link x summed over the shards
     // into lax_ (no-op unsharded), and the cross-shard reduction of scalars

@@ -383,6 +383,123 @@ k_qp_directions(int m, int n, double mu, const double* __restrict__ x, const dou
     if (threadIdx.x == 0) part[blockIdx.x] = th;
 }
 
+// ---------------------------------------------------------------- pc
+// Mehrotra's predictor-corrector (run_pc).  SW: the solver holds the factor
+// with the roles of x and y swapped (a solver with Q, as run_qp): the x
+// block's right-hand side goes in negated and the solve leaves -dy.
+//
+// Right-hand sides of the Newton system: rho + w - cy / y for the rows,
+// sigma - z + cx / x for the columns, with the centring terms
+// cx = mu - dxa dza, cy = mu - dya dwa when mup (scal_'s kIsPcMu) is given;
+// without it the predictor's, which also writes D = z / x and E = w / y.
+template <bool SW>
+__global__ void __launch_bounds__(NT)
+k_pc_rhs(int m, int n, const double* __restrict__ mup, const double* __restrict__ x, const double* __restrict__ z,
+         const double* __restrict__ y, const double* __restrict__ w, const double* __restrict__ rho,
+         const double* __restrict__ sig, double* __restrict__ D, double* __restrict__ E,
+         const double* __restrict__ dxa, const double* __restrict__ dza, const double* __restrict__ dya,
+         const double* __restrict__ dwa, double* __restrict__ fx, double* __restrict__ fy) {
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i < n) {
+        double v = sig[i] - z[i];
+        if (mup) v += (*mup - dxa[i] * dza[i]) / x[i];
+        else D[i] = z[i] / x[i];
+        fx[i] = SW ? -v : v;
+    } else if (i < n + m) {
+        const int j = i - n;
+        double v = rho[j] + w[j];
+        if (mup) v -= (*mup - dya[j] * dwa[j]) / y[j];
+        else E[j] = w[j] / y[j];
+        fy[j] = v;
+    }
+}
+
+// the predictor's dza = -z - D dxa, dwa = -w - E dya and its ratio test (dya
+// stored back with its sign when SW)
+template <bool SW>
+__global__ void __launch_bounds__(NT)
+k_pc_affine(int m, int n, const double* __restrict__ x, const double* __restrict__ z, const double* __restrict__ y,
+            const double* __restrict__ w, const double* __restrict__ D, const double* __restrict__ E,
+            const double* __restrict__ dxa, double* __restrict__ dya, double* __restrict__ dza,
+            double* __restrict__ dwa, double* __restrict__ part) {
+    __shared__ double sh[4];
+    double th = 0.0;
+    for (int i = blockIdx.x * NT + threadIdx.x; i < m + n; i += kRedBlocks * NT) {
+        if (i < n) {
+            const double v = -z[i] - D[i] * dxa[i];
+            dza[i] = v;
+            th = fmax(th, -dxa[i] / x[i]);
+            th = fmax(th, -v / z[i]);
+        } else {
+            const int j = i - n;
+            const double ddy = SW ? -dya[j] : dya[j];
+            const double v = -w[j] - E[j] * ddy;
+            if (SW) dya[j] = ddy;
+            dwa[j] = v;
+            th = fmax(th, -ddy / y[j]);
+            th = fmax(th, -v / w[j]);
+        }
+    }
+    th = block_max(th, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = th;
+}
+
+// the corrected dz = cx / x - z - D dx, dw = cy / y - w - E dy and their
+// ratio test (dy stored back with its sign when SW); mup: kIsPcMu
+template <bool SW>
+__global__ void __launch_bounds__(NT)
+k_pc_directions(int m, int n, const double* __restrict__ mup, const double* __restrict__ x,
+                const double* __restrict__ z, const double* __restrict__ y, const double* __restrict__ w,
+                const double* __restrict__ D, const double* __restrict__ E, const double* __restrict__ dxa,
+                const double* __restrict__ dza, const double* __restrict__ dya, const double* __restrict__ dwa,
+                const double* __restrict__ dx, double* __restrict__ dy, double* __restrict__ dz,
+                double* __restrict__ dw, double* __restrict__ part) {
+    __shared__ double sh[4];
+    const double mu = *mup;
+    double th = 0.0;
+    for (int i = blockIdx.x * NT + threadIdx.x; i < m + n; i += kRedBlocks * NT) {
+        if (i < n) {
+            const double v = (mu - dxa[i] * dza[i]) / x[i] - z[i] - D[i] * dx[i];
+            dz[i] = v;
+            th = fmax(th, -dx[i] / x[i]);
+            th = fmax(th, -v / z[i]);
+        } else {
+            const int j = i - n;
+            const double ddy = SW ? -dy[j] : dy[j];
+            const double v = (mu - dya[j] * dwa[j]) / y[j] - w[j] - E[j] * ddy;
+            if (SW) dy[j] = ddy;
+            dw[j] = v;
+            th = fmax(th, -ddy / y[j]);
+            th = fmax(th, -v / w[j]);
+        }
+    }
+    th = block_max(th, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = th;
+}
+
+// The centring parameter on the device: reads the predictor's largest ratio
+// (kIsPcRatio), the six dots of kIsPcDots and gamma's two (kIsZx, kIsWy, the
+// host's sum); theta_a = 1 if t <= 1 else 1 / t, gamma_a = gamma + theta_a
+// (g1 + theta_a g2), s = min(1, max(0, gamma_a / gamma))^3; writes kIsPcMu =
+// s gamma / denom
+__global__ void k_pc_mu(double* sc, double denom) {
+    const double t = sc[kIsPcRatio];
+    const double ta = t <= 1.0 ? 1.0 : 1.0 / t;
+    const double* d = sc + kIsPcDots;
+    const double gamma = sc[kIsZx] + sc[kIsWy];
+    const double g1 = d[0] + d[1] + d[2] + d[3], g2 = d[4] + d[5];
+    const double ga = gamma + ta * (g1 + ta * g2);
+    const double s = fmin(1.0, fmax(0.0, ga / gamma));
+    sc[kIsPcMu] = s * s * s * gamma / denom;
+}
+
+// theta = min(1, 0.95 / t) from the corrected directions' largest ratio
+// (kIsRed's first), 1 if t = 0; writes kIsTheta
+__global__ void k_pc_theta(double* sc) {
+    const double t = sc[kIsRed];
+    sc[kIsTheta] = (t == 0.0 || 0.95 / t > 1.0) ? 1.0 : 0.95 / t;
+}
+
 // host copy of ls_step for the (phi, psi) pair (hsdls.c:229)
 double ls_step_host(double xj, double zj, double dxj, double dzj, double beta, double delta, double mu) {
     const double a = dxj * dzj;
@@ -534,7 +651,9 @@ int IpmSolver::run(const IpmOptions& opt, IpmResult* res) {
     *res = IpmResult();
     const bool qp = opt.method == Method::Qp;
     if (qp && sharded_) throw std::invalid_argument("qp: not supported on a sharded solver");
-    if (!qp && has_q_) throw std::invalid_argument("a solver built with Q runs method qp only (hsd, intpt and hsdls are LP methods)");
+    const bool pc = opt.method == Method::Pc;
+    if (pc && sharded_) throw std::invalid_argument("pc: not supported on a sharded solver");
+    if (!qp && !pc && has_q_) throw std::invalid_argument("a solver built with Q runs method qp only (hsd, intpt and hsdls are LP methods)");
     KktDevice& K = *kkt_;
     res->t_setup_s = t_setup_;
     K.enable_timing(opt.timing);
@@ -543,6 +662,7 @@ int IpmSolver::run(const IpmOptions& opt, IpmResult* res) {
     const double t0 = now_s();
     // an empty Q is the LP: intpt's iteration on the LP's factor
     const int st = qp                            ? (has_q_ ? run_qp(opt, res) : run_intpt(opt, res))
+                   : pc                          ? (has_q_ ? run_pc<true>(opt, res) : run_pc<false>(opt, res))
                    : opt.method == Method::Intpt ? run_intpt(opt, res)
                    : opt.method == Method::Hsdls ? run_hsdls(opt, res)
                                                  : run_hsd(opt, res);
@@ -967,6 +1087,132 @@ int IpmSolver::run_qp(const IpmOptions& opt, IpmResult* res) {
         theta = (r / theta > 1.0) ? 1.0 : r / theta;
         hipLaunchKernelGGL(k_step, dim3(gv), dim3(NT), 0, s, m, n, theta, static_cast<const double*>(nullptr), x_.get(), dx_.get(), z_.get(), dz_.get(),
                            y_.get(), dy_.get(), w_.get(), dw_.get());
+        normr0 = normr;
+        norms0 = norms;
+    }
+    IPO_HIP_CHECK(hipGetLastError());
+    IPO_HIP_CHECK(hipStreamSynchronize(s));
+    res->iters = iter;
+    return status;
+}
+
+// Mehrotra's predictor-corrector for the problems of run_intpt (SW false: no
+// Q, the LP's factor) and run_qp (SW true: the swapped factor, its calling
+// convention as there); an extension, DESIGN.md §10.2.  Each iteration opens
+// as theirs: the same start, residuals, gamma, objectives, printed line and
+// stop rule.  The give-up tests also ask that the residual stand above
+// 1e-6 (1 + its norm on line 0): a residual at its rounding floor grows
+// tenfold on noise.  Then one factorisation and two refined solves:
+//   predictor  right-hand sides rho + w, sigma - z; dza = -z - D dxa,
+//              dwa = -w - E dya; t = the largest ratio (k_pc_affine)
+//   centring   mu on the device from t, gamma and six dots (k_pc_mu)
+//   corrector  right-hand sides rho + w - cy / y, sigma - z + cx / x with
+//              cx = mu - dxa dza, cy = mu - dya dwa; dz = cx / x - z - D dx,
+//              dw = cy / y - w - E dy; theta = min(1, 0.95 / t) (k_pc_theta)
+// The predictor's dxa, dya live in gx_, gy_ (solved in place) and dza, dwa in
+// fx_, fy_, so they survive the second solve in dx_, dy_.  One host
+// synchronisation an iteration outside the KKT solver, the opening one: the
+// predictor's scalars, mu and theta never leave the device.
+template <bool SW>
+int IpmSolver::run_pc(const IpmOptions& opt, IpmResult* res) {
+    const int m = m_, n = n_;
+    hipStream_t s = stream_;
+    const int gv = ceil_div(m + n, NT);
+    FILE* tr = opt.trace;
+    for (DevBuf<double>* v : {&x_, &z_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(n, NT)), dim3(NT), 0, s, n, 1000.0, v->get());
+    for (DevBuf<double>* v : {&y_, &w_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(m, NT)), dim3(NT), 0, s, m, 1000.0, v->get());
+    double normr0 = HUGE_VAL, norms0 = HUGE_VAL, normr1 = 0.0, norms1 = 0.0;
+    if (tr) {
+        print_dims(tr);
+        std::fputs(kIntptHeader, tr);
+        std::fflush(tr);
+    }
+    KktDevice& K = *kkt_;
+    double* sc = scal_.get();
+    const double* mup = sc + kIsPcMu;
+    const double* nomu = nullptr;
+    int status = 5, iter;
+    for (iter = 0; iter < opt.max_iter; iter++) {
+        row_ax(x_.get(), s);
+        if (SW) {
+            if (K.q_long_count() > 0) K.launch_q_long(x_.get(), qx_.get());     // Q's long columns, one wave each
+            hipLaunchKernelGGL(k_qp_residuals, dim3(kRedBlocks), dim3(kResThreads), 0, s, m, n, K.kA(), K.iA(), K.A(),
+                               K.kAt(), K.iAt(), K.At(), K.kQ(), K.iQ(), K.Q(), b_.get(), c_.get(), x_.get(), y_.get(),
+                               w_.get(), z_.get(), rho_.get(), sig_.get(), qx_.get(), part_.get(), mrow(), lax(),
+                               K.q_long_min());
+        } else {
+            hipLaunchKernelGGL(k_pf_residuals, dim3(kRedBlocks), dim3(kResThreads), 0, s, m, n, K.kAt(), K.iAt(), K.At(),
+                               K.kA(), K.iA(), K.A(), b_.get(), c_.get(), x_.get(), y_.get(), w_.get(), z_.get(),
+                               rho_.get(), sig_.get(), part_.get(), mrow(), mcnt_, lax());
+        }
+        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 2, 0u, sc + kIsNorm2);
+        RedJobs j{};
+        j.nj = SW ? 5 : 4;
+        j.segmin = dot_segmin_;
+        j.a[0] = z_.get(); j.b[0] = x_.get(); j.len[0] = n; j.op[0] = 0;
+        j.a[1] = y_.get(); j.b[1] = w_.get(); j.len[1] = m; j.op[1] = 0;
+        j.a[2] = c_.get(); j.b[2] = x_.get(); j.len[2] = n; j.op[2] = 0;
+        j.a[3] = b_.get(); j.b[3] = y_.get(); j.len[3] = m; j.op[3] = 0;
+        j.a[4] = x_.get(); j.b[4] = qx_.get(); j.len[4] = n; j.op[4] = 0;     // x'Qx (SW)
+        launch_reduce(j, part_.get(), sc, s);
+        IPO_HIP_CHECK(hipMemcpyAsync(hs_, sc, (kIsNorm2 + 2) * sizeof(double), hipMemcpyDeviceToHost, s));
+        IPO_HIP_CHECK(hipStreamSynchronize(s));
+        // the printed quantities in single precision, as run_intpt (intpt.c:47)
+        const float normr = static_cast<float>(std::sqrt(hs_[kIsNorm2]));
+        const float norms = static_cast<float>(std::sqrt(hs_[kIsNorm2 + 1]));
+        const double gamma = hs_[kIsZx] + hs_[kIsWy];
+        const double hxqx = SW ? 0.5 * hs_[kIsXqx] : 0.0;
+        const float pobj = static_cast<float>(hs_[kIsCx] - hxqx + f_);
+        const float dobj = static_cast<float>(hs_[kIsBy] + hxqx + f_);
+        if (tr) {
+            std::fprintf(tr, "%8d   %14.7e  %8.1e    %14.7e  %8.1e \n", iter, pobj, normr, dobj, norms);
+            std::fflush(tr);
+        }
+        res->final_mu = gamma; res->final_pobj = pobj; res->final_dobj = dobj;
+        res->final_pinf = normr; res->final_dinf = norms;
+        if (iter == 0) { normr1 = normr; norms1 = norms; }
+        if (normr < 1.0e-6 && norms < 1.0e-6 && gamma < 1.0e-6) { status = 0; break; }
+        if (normr > 10 * normr0 && normr >= 1.0e-6 * (1.0 + normr1)) { status = 2; break; }
+        if (norms > 10 * norms0 && norms >= 1.0e-6 * (1.0 + norms1)) { status = 4; break; }
+        // the predictor: dxa in gx_, dya in gy_
+        hipLaunchKernelGGL(k_pc_rhs<SW>, dim3(gv), dim3(NT), 0, s, m, n, nomu, x_.get(), z_.get(), y_.get(), w_.get(),
+                           rho_.get(), sig_.get(), D_.get(), E_.get(), nomu, nomu, nomu, nomu, gx_.get(), gy_.get());
+        if (SW) {
+            K.factor(D_.get(), E_.get());
+            K.solve(D_.get(), E_.get(), gx_.get(), gy_.get());
+        } else {
+            K.factor(E_.get(), D_.get());
+            K.solve(E_.get(), D_.get(), gy_.get(), gx_.get());
+        }
+        res->refine_passes += K.last_passes();
+        hipLaunchKernelGGL(k_pc_affine<SW>, dim3(kRedBlocks), dim3(NT), 0, s, m, n, x_.get(), z_.get(), y_.get(), w_.get(),
+                           D_.get(), E_.get(), gx_.get(), gy_.get(), fx_.get(), fy_.get(), part_.get());
+        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 1, 1u, sc + kIsPcRatio);
+        RedJobs g{};
+        g.nj = 6;
+        g.segmin = dot_segmin_;
+        g.a[0] = z_.get(); g.b[0] = gx_.get(); g.len[0] = n; g.op[0] = 0;
+        g.a[1] = x_.get(); g.b[1] = fx_.get(); g.len[1] = n; g.op[1] = 0;
+        g.a[2] = w_.get(); g.b[2] = gy_.get(); g.len[2] = m; g.op[2] = 0;
+        g.a[3] = y_.get(); g.b[3] = fy_.get(); g.len[3] = m; g.op[3] = 0;
+        g.a[4] = gx_.get(); g.b[4] = fx_.get(); g.len[4] = n; g.op[4] = 0;
+        g.a[5] = gy_.get(); g.b[5] = fy_.get(); g.len[5] = m; g.op[5] = 0;
+        launch_reduce(g, part_.get(), sc + kIsPcDots, s);
+        hipLaunchKernelGGL(k_pc_mu, dim3(1), dim3(1), 0, s, sc, static_cast<double>(n + m));
+        // the corrector, with the same factor: dx in dx_, dy in dy_
+        hipLaunchKernelGGL(k_pc_rhs<SW>, dim3(gv), dim3(NT), 0, s, m, n, mup, x_.get(), z_.get(), y_.get(), w_.get(),
+                           rho_.get(), sig_.get(), D_.get(), E_.get(), gx_.get(), fx_.get(), gy_.get(), fy_.get(),
+                           dx_.get(), dy_.get());
+        if (SW) K.solve(D_.get(), E_.get(), dx_.get(), dy_.get());
+        else K.solve(E_.get(), D_.get(), dy_.get(), dx_.get());
+        res->refine_passes += K.last_passes();
+        hipLaunchKernelGGL(k_pc_directions<SW>, dim3(kRedBlocks), dim3(NT), 0, s, m, n, mup, x_.get(), z_.get(), y_.get(),
+                           w_.get(), D_.get(), E_.get(), gx_.get(), fx_.get(), gy_.get(), fy_.get(), dx_.get(), dy_.get(),
+                           dz_.get(), dw_.get(), part_.get());
+        hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 1, 1u, sc);
+        hipLaunchKernelGGL(k_pc_theta, dim3(1), dim3(1), 0, s, sc);
+        hipLaunchKernelGGL(k_step, dim3(gv), dim3(NT), 0, s, m, n, 0.0, static_cast<const double*>(sc + kIsTheta), x_.get(),
+                           dx_.get(), z_.get(), dz_.get(), y_.get(), dy_.get(), w_.get(), dw_.get());
         normr0 = normr;
         norms0 = norms;
     }

@@ -29,7 +29,8 @@ STATUS_TEXT = {
     4: "dual infeasible", 5: "iteration limit", 6: "infinite lower bounds - not implemented",
     7: "suboptimal solution",
 }
-METHODS = {"hsd": 0, "intpt": 1, "hsdls": 2, "qp": 3}
+METHODS = {"hsd": 0, "intpt": 1, "hsdls": 2, "qp": 3, "pc": 4}
+Q_METHODS = ("qp", "pc")      # the methods that take a problem with q
 
 
 class IpoHipError(RuntimeError):
@@ -81,7 +82,7 @@ EXPORTED = [
     "ipo_hip_dot_ordered",
     "ipo_hip_kkt_create_q", "ipo_hip_ldlt_set_q", "ipo_hip_symbolic_q", "ipo_hip_mps_quads",
     "ipo_hip_symbolic_tail", "ipo_hip_kkt_schedule",
-    "ipo_hip_solve_qp", "ipo_hip_ctx_create_qp", "ipo_hip_mps_load_qp",
+    "ipo_hip_solve_qp", "ipo_hip_solve_qp_ex", "ipo_hip_ctx_create_qp", "ipo_hip_mps_load_qp",
     "ipo_hip_q_times", "ipo_hip_kkt_q_long", "ipo_hip_ctx_q_long",
 ]
 
@@ -115,6 +116,8 @@ def lib() -> C.CDLL:
     L.ipo_hip_solve_qp.argtypes = [_I, _I, _I, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I,
                                    C.POINTER(Stats)]
     L.ipo_hip_solve_qp.restype = _I
+    L.ipo_hip_solve_qp_ex.argtypes = [_I] + L.ipo_hip_solve_qp.argtypes
+    L.ipo_hip_solve_qp_ex.restype = _I
     L.ipo_hip_ctx_create_qp.argtypes = [_I, _I, _P, _P, _P, _P, _P, _D, _P, _P, _P]
     L.ipo_hip_ctx_create_qp.restype = _P
     L.ipo_hip_mps_load_qp.argtypes = [C.c_char_p, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _P, _P, _P, _P, _P,
@@ -382,7 +385,9 @@ def _capture(fn):
 def run_mps(path: str, method: str = "hsd", timing: bool = False, free: str = "abort", solfile: str = None):
     """Equivalent of `ipo path` (main.c) on the GPU.  Returns (status, stdout text, stats dict).
     free="split": the free-variable extension; solfile: write the writesol report there.
-    method="qp": the file's quadratic program, QUADS included (not with free="split")."""
+    method="qp": the file's quadratic program, QUADS included (not with free="split").
+    method="pc": the predictor-corrector on the same program (a file without
+    QUADS: the LP, which free="split" then takes too)."""
     require_gpu()
     st = Stats()
     fl = SPLIT_FREE if free == "split" else 0
@@ -395,7 +400,8 @@ def run_mps(path: str, method: str = "hsd", timing: bool = False, free: str = "a
 def solver(p: SolverForm, method: str = "hsd", trace: bool = False, max_iter: int = 200, timing: bool = False):
     """solver() on host arrays.  Returns dict(status, x, y, w, z, stats, trace).
     method="qp": the quadratic program with p.q (ipo_hip_solve_qp; an empty Q
-    without it).  A problem with q takes no other method."""
+    without it).  method="pc": the predictor-corrector, with or without p.q.
+    A problem with q takes no other method."""
     require_gpu()
     x = np.zeros(p.n, np.float64)
     z = np.zeros(p.n, np.float64)
@@ -409,15 +415,15 @@ def solver(p: SolverForm, method: str = "hsd", trace: bool = False, max_iter: in
     c = np.ascontiguousarray(p.c, np.float64)
 
     q = getattr(p, "q", None)
-    if q is not None and method != "qp":
-        raise IpoHipError(f"solver: a problem with q takes method 'qp', not '{method}'")
+    if q is not None and method not in Q_METHODS:
+        raise IpoHipError(f"solver: a problem with q takes method 'qp' or 'pc', not '{method}'")
     qa = _q_arrays(q) if q is not None else None
 
     def call(fp):
-        if method == "qp":
-            return lib().ipo_hip_solve_qp(p.m, p.n, p.nz, _ptr(iA), _ptr(kA), _ptr(A), _ptr(b), _ptr(c), float(p.f),
-                                          *([_ptr(a) for a in qa] if qa else [None] * 3), _ptr(x), _ptr(y), _ptr(w),
-                                          _ptr(z), fp, max_iter, int(timing), C.byref(st))
+        if method == "qp" or (method == "pc" and qa):
+            return lib().ipo_hip_solve_qp_ex(METHODS[method], p.m, p.n, p.nz, _ptr(iA), _ptr(kA), _ptr(A), _ptr(b), _ptr(c), float(p.f),
+                                             *([_ptr(a) for a in qa] if qa else [None] * 3), _ptr(x), _ptr(y),
+                                             _ptr(w), _ptr(z), fp, max_iter, int(timing), C.byref(st))
         return lib().ipo_hip_solve(METHODS[method], p.m, p.n, p.nz, _ptr(iA), _ptr(kA), _ptr(A), _ptr(b), _ptr(c),
                                    float(p.f), _ptr(x), _ptr(y), _ptr(w), _ptr(z), fp, max_iter, int(timing),
                                    C.byref(st))
@@ -507,7 +513,7 @@ class KktFactor:
 class Context:
     """Device-resident problem (ipo_hip_ctx): setup once, run() many times.
     A problem with q (SolverForm.q) gives a QP context (ipo_hip_ctx_create_qp),
-    which runs method "qp" only."""
+    which runs methods "qp" and "pc" only."""
 
     def __init__(self, p: SolverForm):
         require_gpu()
