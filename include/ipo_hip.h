@@ -110,7 +110,9 @@ int ipo_hip_solve(int method, int m, int n, int nz, const int *iA, const int *kA
 
 /* Persistent context: uploads the problem to HBM and runs the symbolic
  * analysis once (setup); ipo_hip_ctx_run then iterates from the reference's
- * start point with everything device-resident (used by bench.py). */
+ * start point with everything device-resident (used by bench.py).  One
+ * pattern per context; its numbers can be replaced (ipo_hip_ctx_update) and
+ * the start point chosen (ipo_hip_ctx_set_start) below. */
 typedef struct ipo_hip_ctx ipo_hip_ctx;
 ipo_hip_ctx *ipo_hip_ctx_create(int m, int n, const int *kA, const int *iA, const double *A,
                                 const double *b, const double *c, double f);
@@ -118,6 +120,41 @@ int  ipo_hip_ctx_run(ipo_hip_ctx *ctx, int method, int max_iter, FILE *trace, in
 void ipo_hip_ctx_download(ipo_hip_ctx *ctx, double *x, double *y, double *w, double *z);
 void ipo_hip_ctx_destroy(ipo_hip_ctx *ctx);
 double ipo_hip_ctx_setup_seconds(const ipo_hip_ctx *ctx);
+
+/* New numbers on the context's pattern (an extension): the
+ * symbolic analysis, the plan and every launch schedule depend on the pattern
+ * alone and are kept.  Each argument is NULL (unchanged) or the full array in
+ * the layout given at creation: A[nz] in the creation's kA / iA order, b[m],
+ * c[n], *f, Q[qnz] in the creation's kQ / iQ order.  The next ipo_hip_ctx_run
+ * sees exactly what a context freshly created from the new arrays would
+ * (bit for bit).  The arrays given are uploaded and validated on the device
+ * before anything is replaced: every value finite, Q[k] equal to its
+ * transposed entry.  Refused, with the context still running on its old
+ * numbers: a non-finite value, an asymmetric Q, Q != NULL on a context created
+ * without (or with an empty) Q, any update on a sharded context.  That Q be
+ * positive semidefinite stays the caller's business, as at creation.  Resets
+ * nothing (a start point set below stays).  Returns 0, or -1
+ * (ipo_hip_last_error). */
+int ipo_hip_ctx_update(ipo_hip_ctx *ctx, const double *A, const double *b, const double *c,
+                       const double *f, const double *Q);
+/* wall seconds of the last ipo_hip_ctx_update: its uploads with their
+ * validation, and the device refresh after them (either may be NULL) */
+void ipo_hip_ctx_update_seconds(const ipo_hip_ctx *ctx, double *upload_s, double *refresh_s);
+
+/* A start point for the infeasible-start methods (1 intpt, 3 qp, 4 pc) in
+ * place of "every variable 1000": host vectors x, z (n) and y, w (m), every
+ * entry finite and > 0 (checked on the device; -1 otherwise, and a start set
+ * earlier stays).  All four NULL clears it.  It persists over runs and
+ * updates until cleared; all else in those methods' loops is unchanged.
+ * Methods 0 and 2 (hsd, hsdls), whose state includes phi and psi, return 7
+ * with an error text and no iteration while a start is set.
+ * ipo_hip_ctx_start_from_last takes the iterate the last run left in x, y, w,
+ * z (any method, any status), each entry raised to at least floor > 0, on the
+ * device; -1 before any run.  How far to push a previous optimum back into
+ * the interior is the caller's choice: floor is the lever, no policy is built
+ * in.  Sharded contexts refuse both.  Return 0, or -1 (ipo_hip_last_error). */
+int ipo_hip_ctx_set_start(ipo_hip_ctx *ctx, const double *x, const double *y, const double *w, const double *z);
+int ipo_hip_ctx_start_from_last(ipo_hip_ctx *ctx, double floor);
 
 /* ---- quadratic programs (an extension: the reference has no QP loop) --------
  * Solves  max c'x + f - x'Qx / 2  s.t.  Ax <= b, x >= 0  by intpt.c's
@@ -365,6 +402,26 @@ int ipo_hip_lead_col_targets(int nt, int *out, int cap);
  * an unknown name or an error (ipo_hip_last_error). */
 long ipo_hip_kkt_schedule(int m, int n, const int *kA, const int *iA, int nforced, int cus, const char *name, int *out,
                           long cap);
+
+/* The index maps ipo_hip_ctx_update refreshes a context's value arrays
+ * through, built from a pattern alone (host-only; test entry, no reference
+ * counterpart, no HIP call).  kA / iA: the m x n CSC pattern of A, or for
+ * "qdiag" / "qt" Q's (m = n).  name:
+ *   "csr"    [nz] entry d of the CSR of A (rows ascending, a row's entries in
+ *            CSC order) is CSC entry out[d]
+ *   "jds"    [nz] slice position q of the row products' jagged-diagonal
+ *            layout (IPO_HIP_AX_BLOCKS column slices, read from the
+ *            environment) holds CSC entry out[q]; with it "jds.cols" [nz] the
+ *            column of each position, "jds.perm" [passes m] the row order of
+ *            each pass, "jds.dptr" / "jds.dlen" the diagonals' starts and
+ *            lengths, "jds.dims" = passes, then per pass (rows launched,
+ *            diagonals, offset into dptr / dlen)
+ *   "qdiag"  [n] the entry (j, j) of column j, -1 without one
+ *   "qt"     [qnz] the entry (j, i) for entry k = (i, j); -1 is returned (the
+ *            call fails) on a pattern that is not symmetric
+ * Returns the length (at most cap entries are written to out, which may be
+ * NULL), or -1 (ipo_hip_last_error). */
+long ipo_hip_value_maps(int m, int n, const int *kA, const int *iA, const char *name, int *out, long cap);
 
 int ipo_hip_device_count(void);
 /* hipDeviceSynchronize on the calling thread's device (bench.py brackets its

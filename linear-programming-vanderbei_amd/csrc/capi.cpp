@@ -18,6 +18,7 @@
 #include "kkt_schedule.h"
 #include "lp_io.h"
 #include "synth.h"
+#include "value_maps.h"
 
 namespace {
 
@@ -294,6 +295,42 @@ void ipo_hip_ctx_download(ipo_hip_ctx* ctx, double* x, double* y, double* w, dou
 }
 
 void ipo_hip_ctx_destroy(ipo_hip_ctx* ctx) { delete ctx; }
+
+int ipo_hip_ctx_update(ipo_hip_ctx* ctx, const double* A, const double* b, const double* c, const double* f,
+                       const double* Q) {
+    try {
+        ctx->solver->update(A, b, c, f, Q);
+        return 0;
+    } catch (const std::exception& e) {
+        set_err(e.what());
+        return -1;
+    }
+}
+
+void ipo_hip_ctx_update_seconds(const ipo_hip_ctx* ctx, double* upload_s, double* refresh_s) {
+    if (upload_s) *upload_s = ctx->solver->update_upload_seconds();
+    if (refresh_s) *refresh_s = ctx->solver->update_refresh_seconds();
+}
+
+int ipo_hip_ctx_set_start(ipo_hip_ctx* ctx, const double* x, const double* y, const double* w, const double* z) {
+    try {
+        ctx->solver->set_start(x, y, w, z);
+        return 0;
+    } catch (const std::exception& e) {
+        set_err(e.what());
+        return -1;
+    }
+}
+
+int ipo_hip_ctx_start_from_last(ipo_hip_ctx* ctx, double floor) {
+    try {
+        ctx->solver->start_from_last(floor);
+        return 0;
+    } catch (const std::exception& e) {
+        set_err(e.what());
+        return -1;
+    }
+}
 
 double ipo_hip_ctx_setup_seconds(const ipo_hip_ctx* ctx) { return ctx->solver->setup_seconds(); }
 
@@ -994,6 +1031,45 @@ long ipo_hip_kkt_schedule(int m, int n, const int* kA, const int* iA, int nforce
                 v.insert(v.end(), w.begin(), w.end());
                 b = e + 1;
             }
+        }
+        if (out) std::copy(v.begin(), v.begin() + std::min<long>(cap, static_cast<long>(v.size())), out);
+        return static_cast<long>(v.size());
+    } catch (const std::exception& e) {
+        set_err(e.what());
+        return -1;
+    }
+}
+
+long ipo_hip_value_maps(int m, int n, const int* kA, const int* iA, const char* name, int* out, long cap) {
+    try {
+        if (!name || !kA || m < 0 || n < 0) throw std::invalid_argument("value_maps: bad arguments");
+        if (kA[0] != 0) throw std::invalid_argument("value_maps: the column pointers do not start at 0");
+        for (int j = 0; j < n; j++)
+            if (kA[j + 1] < kA[j]) throw std::invalid_argument("value_maps: column pointers decreasing at column " + std::to_string(j));
+        if (kA[n] > 0 && !iA) throw std::invalid_argument("value_maps: bad arguments");
+        for (int k = 0; k < kA[n]; k++)
+            if (iA[k] < 0 || iA[k] >= m) throw std::invalid_argument("value_maps: row index out of range at entry " + std::to_string(k));
+        const std::string nm(name);
+        std::vector<int> v;
+        if (nm == "csr") {
+            v = ipo::csr_value_map(m, n, kA, iA);
+        } else if (nm == "qdiag" || nm == "qt") {
+            if (m != n) throw std::invalid_argument("value_maps: Q is square");
+            v = nm == "qdiag" ? ipo::q_diag_map(n, kA, iA) : ipo::q_transpose_map(n, kA, iA);
+        } else if (nm.rfind("jds", 0) == 0) {
+            // the layout an IpmSolver of this pattern builds at the environment's IPO_HIP_AX_BLOCKS
+            const ipo::RowAxLayout L = ipo::row_ax_layout(m, n, kA, iA, ipo::KktKnobs::from_env().ax_blocks);
+            if (nm == "jds") v = L.src;
+            else if (nm == "jds.cols") v = L.cols;
+            else if (nm == "jds.perm") v = L.perm;
+            else if (nm == "jds.dptr") v = L.dptr;
+            else if (nm == "jds.dlen") v = L.dlen;
+            else if (nm == "jds.dims") {      // passes, then per pass: rows launched, diagonals, offset into dptr / dlen
+                v.push_back(L.np);
+                for (int p = 0; p < L.np; p++) v.insert(v.end(), {L.rows[p], L.nd[p], L.dbase[p]});
+            } else throw std::invalid_argument("value_maps: unknown map '" + nm + "'");
+        } else {
+            throw std::invalid_argument("value_maps: unknown map '" + nm + "'");
         }
         if (out) std::copy(v.begin(), v.begin() + std::min<long>(cap, static_cast<long>(v.size())), out);
         return static_cast<long>(v.size());

@@ -6,6 +6,7 @@
 #include <stdexcept>
 #include <vector>
 #include "hip_util.h"
+#include "value_maps.h"
 
 namespace ipo {
 
@@ -412,62 +413,26 @@ bool rows_ax_sliced(const KktKnobs& knobs, int n) {
 }
 
 void RowAxPlan::build(int m, int n, const int* kA, const int* iA, const double* A, int npass, hipStream_t st) {
+    const RowAxLayout L = row_ax_layout(m, n, kA, iA, npass);     // value_maps.h
     m_ = m;
-    np_ = std::max(1, npass);
-    const int per = (n + np_ - 1) / np_;
-    auto slice = [&](int j) { return per > 0 ? std::min(np_ - 1, j / per) : 0; };
-    // entries per (pass, row), the rows of each pass by count (descending,
-    // row order among equal counts), the diagonals
-    std::vector<int> cnt(static_cast<size_t>(np_) * m, 0);
-    for (int j = 0; j < n; j++)
-        for (int k = kA[j]; k < kA[j + 1]; k++) cnt[static_cast<size_t>(slice(j)) * m + iA[k]]++;
-    std::vector<int> perm(static_cast<size_t>(np_) * m), rank(static_cast<size_t>(np_) * m), dptr, dlen;
-    rows_.assign(np_, 0);
-    nd_.assign(np_, 0);
-    dbase_.assign(np_ + 1, 0);
-    long nz = 0;
-    for (int p = 0; p < np_; p++) {
-        const int* c = cnt.data() + static_cast<size_t>(p) * m;
-        int mx = 0;
-        for (int i = 0; i < m; i++) mx = std::max(mx, c[i]);
-        std::vector<int> bucket(mx + 2, 0);          // rows with count >= v start at bucket[mx - v]
-        for (int i = 0; i < m; i++) bucket[mx - c[i] + 1]++;
-        for (int v = 0; v <= mx; v++) bucket[v + 1] += bucket[v];
-        int* pp = perm.data() + static_cast<size_t>(p) * m;
-        int* rk = rank.data() + static_cast<size_t>(p) * m;
-        for (int i = 0; i < m; i++) { const int r = bucket[mx - c[i]]++; pp[r] = i; rk[i] = r; }
-        // pass 0 writes every row (a row with no entry in it gets 0); later
-        // passes only the rows that have entries in their slice
-        int active = 0;
-        while (active < m && c[pp[active]] > 0) active++;
-        rows_[p] = p == 0 ? m : active;
-        nd_[p] = mx;
-        for (int k = 0, len = active; k < mx; k++) {
-            while (len > 0 && c[pp[len - 1]] <= k) len--;
-            dptr.push_back(static_cast<int>(nz));
-            dlen.push_back(len);
-            nz += len;
-        }
-        dbase_[p + 1] = static_cast<int>(dptr.size());
-    }
-    if (nz > static_cast<long>(INT32_MAX)) throw std::length_error("row products: more than 2^31 entries");
-    std::vector<int> cols(nz), fill(static_cast<size_t>(np_) * m, 0);
-    std::vector<double> vals(nz);
-    for (int j = 0; j < n; j++) {
-        const int p = slice(j);
-        for (int k = kA[j]; k < kA[j + 1]; k++) {
-            const size_t pi = static_cast<size_t>(p) * m + iA[k];
-            const int q = dptr[dbase_[p] + fill[pi]++] + rank[pi];
-            cols[q] = j;
-            vals[q] = A[k];
-        }
-    }
-    perm_.upload(perm, st);
-    dptr_.upload(dptr, st);
-    dlen_.upload(dlen, st);
-    cols_.upload(cols, st);
+    np_ = L.np;
+    rows_ = L.rows;
+    nd_ = L.nd;
+    dbase_ = L.dbase;
+    nz_ = static_cast<int>(L.src.size());
+    std::vector<double> vals(L.src.size());
+    for (size_t q = 0; q < L.src.size(); q++) vals[q] = A[L.src[q]];
+    perm_.upload(L.perm, st);
+    dptr_.upload(L.dptr, st);
+    dlen_.upload(L.dlen, st);
+    cols_.upload(L.cols, st);
+    src_.upload(L.src, st);
     vals_.upload(vals, st);
     IPO_HIP_CHECK(hipStreamSynchronize(st));     // the host vectors go out of scope
+}
+
+void RowAxPlan::refresh(const double* dA, hipStream_t st) {
+    launch_gather_map(nz_, src_.get(), dA, vals_.get(), st);
 }
 
 void RowAxPlan::launch(const double* x, double* ax, hipStream_t st) const {

@@ -103,6 +103,31 @@ class IpmSolver {
     void download(double* x, double* y, double* w, double* z) const;
     KktDevice& kkt() { return *kkt_; }
     double setup_seconds() const { return t_setup_; }
+    // New numbers on the constructor's pattern (ipo_hip_ctx_update; DESIGN.md
+    // 10.3): each argument null (unchanged) or the full host array in the
+    // constructor's layout, Q in q's kQ / iQ order.  The arrays given are
+    // uploaded to staging buffers and validated there on the device (every
+    // value finite, Q[k] == Q[its transposed entry]); only then are A and its
+    // CSR copy, the RowAxPlan slices, Q and its diagonal, b, c and f replaced,
+    // so after a throw (std::invalid_argument: a bad value, Q for a solver
+    // without Q, a sharded solver) the solver runs with its old numbers.
+    // The next run() sees what a solver constructed from the new arrays would.
+    void update(const double* A, const double* b, const double* c, const double* f, const double* Q);
+    // seconds of the last update(): the uploads with their validation, and the
+    // device refresh that followed (both ended by a stream synchronisation)
+    double update_upload_seconds() const { return t_upd_upload_; }
+    double update_refresh_seconds() const { return t_upd_refresh_; }
+    // The start point of the infeasible-start methods (Intpt, Qp, Pc) in place
+    // of every variable 1000: host vectors x, z (n), y, w (m), every entry
+    // finite and > 0 (checked on the device before the held start is
+    // replaced; std::invalid_argument otherwise, and on a sharded solver).
+    // All four null: back to the default.  It persists until cleared; Hsd and
+    // Hsdls, whose state includes phi and psi, refuse to run while one is set.
+    void set_start(const double* x, const double* y, const double* w, const double* z);
+    // ... the iterate the last run() left, raised entry by entry to at least
+    // floor > 0 (one kernel, no host round trip).  Throws before any run().
+    void start_from_last(double floor);
+    bool has_start() const { return has_start_; }
 
   private:
     int run_hsd(const IpmOptions& opt, IpmResult* res);
@@ -129,6 +154,20 @@ class IpmSolver {
     DevBuf<double> ax_;
     RowAxPlan axplan_;
     void print_dims(FILE* tr) const;
+    // x, z, y, w of a path-following run's line 0: the held start, or v everywhere
+    void init_point(double v);
+    void alloc_start();
+    // the value maps of update() (value_maps.h), uploaded at construction
+    int nz_ = 0, qnz_ = 0;
+    DevBuf<int> ucsr_;           // has_q_: the factor's "A" (the CSR of A) from the caller's CSC
+    DevBuf<int> qtmap_;          // has_q_: Q entry -> its transposed entry
+    // update()'s staging (allocated by the first update that needs each)
+    DevBuf<double> stA_, stAt_, stb_, stc_, stQ_;
+    DevBuf<int> vfirst_;         // [kVfCount] first offending index of each validation
+    double t_upd_upload_ = 0.0, t_upd_refresh_ = 0.0;
+    // the start point: held (sx_ ...) and set_start()'s staging (tx_ ...)
+    bool has_start_ = false, ran_ = false;
+    DevBuf<double> sx_, sy_, sw_, sz_, tx_, ty_, tw_, tz_;
 
     int m_, n_;
     double f_;

@@ -17,12 +17,15 @@
 #include <cstring>
 #include <exception>
 #include <stdexcept>
+#include <string>
+#include <utility>
 #include <vector>
 
 #include "dev_common.h"
 #include "hip_util.h"
 #include "ipm.h"
 #include "lp_io.h"
+#include "value_maps.h"
 
 namespace ipo {
 
@@ -539,6 +542,7 @@ IpmSolver::IpmSolver(int m, int n, const int* kA, const int* iA, const double* A
     mg_ = m;
     ng_ = n;
     nzg_ = kA[n];
+    nz_ = kA[n];
     mcnt_ = m;
     if (shard) {
         if (shard->nforced < 0 || shard->nforced > m) throw std::invalid_argument("shard: nforced out of range");
@@ -567,6 +571,12 @@ IpmSolver::IpmSolver(int m, int n, const int* kA, const int* iA, const double* A
         QBlock qb = *q;
         qb.qmax = 1;
         kkt_ = std::make_unique<KktDevice>(n, m, kat.data(), iat.data(), at.data(), stream_, 0, &qb);
+        // update()'s maps: at = A[ucsr], and Q's transposed entries
+        qnz_ = q->kQ[n];
+        const std::vector<int> ucsr = csr_value_map(m, n, kA, iA), qt = q_transpose_map(n, q->kQ, q->iQ);
+        ucsr_.upload(ucsr, stream_);
+        qtmap_.upload(qt, stream_);
+        IPO_HIP_CHECK(hipStreamSynchronize(stream_));   // locals
     } else {
         kkt_ = std::make_unique<KktDevice>(m, n, kA, iA, A, stream_, nforced_);
         kkt_->set_exchange(xch_);
@@ -654,6 +664,9 @@ int IpmSolver::run(const IpmOptions& opt, IpmResult* res) {
     const bool pc = opt.method == Method::Pc;
     if (pc && sharded_) throw std::invalid_argument("pc: not supported on a sharded solver");
     if (!qp && !pc && has_q_) throw std::invalid_argument("a solver built with Q runs method qp only (hsd, intpt and hsdls are LP methods)");
+    if (has_start_ && !qp && !pc && opt.method != Method::Intpt)
+        throw std::invalid_argument("a start point is set: hsd and hsdls take none (their state includes phi and psi); "
+                                    "clear it, or run intpt, qp or pc");
     KktDevice& K = *kkt_;
     res->t_setup_s = t_setup_;
     K.enable_timing(opt.timing);
@@ -669,7 +682,139 @@ int IpmSolver::run(const IpmOptions& opt, IpmResult* res) {
     res->t_solve_s = now_s() - t0;
     res->status = st;
     res->kkt = K.timers();
+    ran_ = true;
     return st;
+}
+
+void IpmSolver::init_point(double v) {
+    hipStream_t s = stream_;
+    const int m = m_, n = n_;
+    if (has_start_) {
+        const std::pair<DevBuf<double>*, const DevBuf<double>*> cp[] = {{&x_, &sx_}, {&z_, &sz_}, {&y_, &sy_}, {&w_, &sw_}};
+        for (const auto& c : cp) {
+            const size_t len = (c.first == &x_ || c.first == &z_) ? n : m;
+            if (len) IPO_HIP_CHECK(hipMemcpyAsync(c.first->get(), c.second->get(), len * sizeof(double), hipMemcpyDeviceToDevice, s));
+        }
+        return;
+    }
+    for (DevBuf<double>* p : {&x_, &z_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(n, NT)), dim3(NT), 0, s, n, v, p->get());
+    for (DevBuf<double>* p : {&y_, &w_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(m, NT)), dim3(NT), 0, s, m, v, p->get());
+}
+
+namespace {
+// the slots of IpmSolver::vfirst_
+constexpr int kVfA = 0, kVfB = 1, kVfC = 2, kVfQ = 3, kVfQsym = 4, kVfX = 5, kVfY = 6, kVfW = 7, kVfZ = 8, kVfCount = 9;
+constexpr int kVfNone = 0x7f7f7f7f;      // a slot no kernel lowered (memset 0x7f)
+}  // namespace
+
+void IpmSolver::update(const double* A, const double* b, const double* c, const double* f, const double* Q) {
+    if (sharded_)
+        throw std::invalid_argument("update: not supported on a sharded solver (a shard keeps the values it was created with)");
+    if (Q && !has_q_) throw std::invalid_argument("update: Q given to a solver created without Q");
+    if (f && !std::isfinite(*f)) throw std::invalid_argument("update: f is not finite");
+    hipStream_t s = stream_;
+    const double t0 = now_s();
+    const int m = m_, n = n_;
+    // 1. the arrays given, into staging; 2. validated there
+    if (vfirst_.size() == 0) vfirst_.alloc(kVfCount);
+    IPO_HIP_CHECK(hipMemsetAsync(vfirst_.get(), 0x7f, kVfCount * sizeof(int), s));    // kVfNone
+    int* vf = vfirst_.get();
+    if (A) { stA_.upload(A, nz_, s); launch_first_nonfinite(nz_, stA_.get(), vf + kVfA, s); }
+    if (b) { stb_.upload(b, m, s); launch_first_nonfinite(m, stb_.get(), vf + kVfB, s); }
+    if (c) { stc_.upload(c, n, s); launch_first_nonfinite(n, stc_.get(), vf + kVfC, s); }
+    if (Q) {
+        stQ_.upload(Q, qnz_, s);
+        launch_first_nonfinite(qnz_, stQ_.get(), vf + kVfQ, s);
+        launch_first_asymmetric(qnz_, stQ_.get(), qtmap_.get(), vf + kVfQsym, s);
+    }
+    int first[kVfCount];
+    IPO_HIP_CHECK(hipMemcpyAsync(first, vf, sizeof first, hipMemcpyDeviceToHost, s));
+    IPO_HIP_CHECK(hipStreamSynchronize(s));
+    t_upd_upload_ = now_s() - t0;
+    t_upd_refresh_ = 0.0;
+    const auto refuse = [&](int slot, int len, const char* what, const char* why) {
+        if (first[slot] != kVfNone && first[slot] < len)
+            throw std::invalid_argument(std::string("update: ") + what + "[" + std::to_string(first[slot]) + "] " + why);
+    };
+    if (A) refuse(kVfA, nz_, "A", "is not finite");
+    if (b) refuse(kVfB, m, "b", "is not finite");
+    if (c) refuse(kVfC, n, "c", "is not finite");
+    if (Q) {
+        refuse(kVfQ, qnz_, "Q", "is not finite");
+        refuse(kVfQsym, qnz_, "Q", "differs from its transposed entry (Q is not symmetric)");
+    }
+    // 3. committed: copies and gathers on the stream, nothing can refuse now
+    const double t1 = now_s();
+    const double* dAk = nullptr;      // A in the factor's own CSC order
+    if (A) {
+        if (has_q_) {                 // the factor holds A' (run_qp): its "A" is the CSR of A
+            if (stAt_.size() < static_cast<size_t>(nz_)) stAt_.alloc(nz_);
+            launch_gather_map(nz_, ucsr_.get(), stA_.get(), stAt_.get(), s);
+            dAk = stAt_.get();
+        } else {
+            dAk = stA_.get();
+        }
+        if (axsliced_) axplan_.refresh(stA_.get(), s);
+    }
+    kkt_->refresh_values(dAk, Q ? stQ_.get() : nullptr);
+    if (b && m) IPO_HIP_CHECK(hipMemcpyAsync(b_.get(), stb_.get(), m * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (c && n) IPO_HIP_CHECK(hipMemcpyAsync(c_.get(), stc_.get(), n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (f) f_ = *f;
+    IPO_HIP_CHECK(hipStreamSynchronize(s));
+    t_upd_refresh_ = now_s() - t1;
+}
+
+void IpmSolver::alloc_start() {
+    const size_t mm = m_ > 0 ? m_ : 1, nn = n_ > 0 ? n_ : 1;
+    if (sx_.size()) return;
+    for (DevBuf<double>* v : {&sx_, &sz_, &tx_, &tz_}) v->alloc(nn);
+    for (DevBuf<double>* v : {&sy_, &sw_, &ty_, &tw_}) v->alloc(mm);
+}
+
+void IpmSolver::set_start(const double* x, const double* y, const double* w, const double* z) {
+    if (sharded_) throw std::invalid_argument("set_start: not supported on a sharded solver");
+    if (!x && !y && !w && !z) { has_start_ = false; return; }
+    if (!x || !y || !w || !z) throw std::invalid_argument("set_start: x, y, w and z are given together (all null clears the start)");
+    hipStream_t s = stream_;
+    const int m = m_, n = n_;
+    alloc_start();
+    if (vfirst_.size() == 0) vfirst_.alloc(kVfCount);
+    IPO_HIP_CHECK(hipMemsetAsync(vfirst_.get(), 0x7f, kVfCount * sizeof(int), s));
+    int* vf = vfirst_.get();
+    tx_.upload(x, n, s); launch_first_nonpositive(n, tx_.get(), vf + kVfX, s);
+    ty_.upload(y, m, s); launch_first_nonpositive(m, ty_.get(), vf + kVfY, s);
+    tw_.upload(w, m, s); launch_first_nonpositive(m, tw_.get(), vf + kVfW, s);
+    tz_.upload(z, n, s); launch_first_nonpositive(n, tz_.get(), vf + kVfZ, s);
+    int first[kVfCount];
+    IPO_HIP_CHECK(hipMemcpyAsync(first, vf, sizeof first, hipMemcpyDeviceToHost, s));
+    IPO_HIP_CHECK(hipStreamSynchronize(s));
+    const std::pair<int, const char*> chk[] = {{kVfX, "x"}, {kVfY, "y"}, {kVfW, "w"}, {kVfZ, "z"}};
+    for (const auto& c : chk)
+        if (first[c.first] != kVfNone && first[c.first] < ((c.first == kVfX || c.first == kVfZ) ? n : m))
+            throw std::invalid_argument(std::string("set_start: ") + c.second + "[" + std::to_string(first[c.first]) +
+                                        "] is not a finite value > 0");
+    ClampJobs J{};       // the copy into the held start: floor 0 leaves positive values as they are
+    J.src[0] = tx_.get(); J.dst[0] = sx_.get(); J.len[0] = n;
+    J.src[1] = ty_.get(); J.dst[1] = sy_.get(); J.len[1] = m;
+    J.src[2] = tw_.get(); J.dst[2] = sw_.get(); J.len[2] = m;
+    J.src[3] = tz_.get(); J.dst[3] = sz_.get(); J.len[3] = n;
+    launch_clamp_copy4(J, 0.0, s);
+    IPO_HIP_CHECK(hipStreamSynchronize(s));
+    has_start_ = true;
+}
+
+void IpmSolver::start_from_last(double floor) {
+    if (sharded_) throw std::invalid_argument("start_from_last: not supported on a sharded solver");
+    if (!ran_) throw std::invalid_argument("start_from_last: no run on this solver yet");
+    if (!(floor > 0.0) || !std::isfinite(floor)) throw std::invalid_argument("start_from_last: floor must be finite and > 0");
+    alloc_start();
+    ClampJobs J{};
+    J.src[0] = x_.get(); J.dst[0] = sx_.get(); J.len[0] = n_;
+    J.src[1] = y_.get(); J.dst[1] = sy_.get(); J.len[1] = m_;
+    J.src[2] = w_.get(); J.dst[2] = sw_.get(); J.len[2] = m_;
+    J.src[3] = z_.get(); J.dst[3] = sz_.get(); J.len[3] = n_;
+    launch_clamp_copy4(J, floor, stream_);
+    has_start_ = true;
 }
 
 int IpmSolver::run_hsd(const IpmOptions& opt, IpmResult* res) {
@@ -943,8 +1088,7 @@ int IpmSolver::run_intpt(const IpmOptions& opt, IpmResult* res) {
     hipStream_t s = stream_;
     const int gv = ceil_div(m + n, NT);
     FILE* tr = opt.trace;
-    for (DevBuf<double>* v : {&x_, &z_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(n, NT)), dim3(NT), 0, s, n, 1000.0, v->get());
-    for (DevBuf<double>* v : {&y_, &w_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(m, NT)), dim3(NT), 0, s, m, 1000.0, v->get());
+    init_point(1000.0);
     const double delta = 0.02, r = 0.9;
     double normr0 = HUGE_VAL, norms0 = HUGE_VAL;
     if (tr) {
@@ -1027,8 +1171,7 @@ int IpmSolver::run_qp(const IpmOptions& opt, IpmResult* res) {
     hipStream_t s = stream_;
     const int gv = ceil_div(m + n, NT);
     FILE* tr = opt.trace;
-    for (DevBuf<double>* v : {&x_, &z_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(n, NT)), dim3(NT), 0, s, n, 1000.0, v->get());
-    for (DevBuf<double>* v : {&y_, &w_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(m, NT)), dim3(NT), 0, s, m, 1000.0, v->get());
+    init_point(1000.0);
     const double delta = 0.02, r = 0.9;
     double normr0 = HUGE_VAL, norms0 = HUGE_VAL;
     if (tr) {
@@ -1119,8 +1262,7 @@ int IpmSolver::run_pc(const IpmOptions& opt, IpmResult* res) {
     hipStream_t s = stream_;
     const int gv = ceil_div(m + n, NT);
     FILE* tr = opt.trace;
-    for (DevBuf<double>* v : {&x_, &z_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(n, NT)), dim3(NT), 0, s, n, 1000.0, v->get());
-    for (DevBuf<double>* v : {&y_, &w_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(m, NT)), dim3(NT), 0, s, m, 1000.0, v->get());
+    init_point(1000.0);
     double normr0 = HUGE_VAL, norms0 = HUGE_VAL, normr1 = 0.0, norms1 = 0.0;
     if (tr) {
         print_dims(tr);

@@ -209,6 +209,12 @@ class KktDevice {
         hipStream_t stream = nullptr;     // the side stream (not the object's)
         hipEvent_t ready = nullptr;       // recorded once dfy / dfx hold the right-hand sides
     };
+    // New values on the constructor's pattern: dA (its CSC order) and dQ (its
+    // kQ / iQ order) are device arrays, validated by the caller (finite, Q
+    // symmetric); null: unchanged.  The next factor() and the residual
+    // kernels then see what a KktDevice built from those values would.
+    void refresh_values(const double* dA, const double* dQ);
+    int qnz() const { return qnz_; }
     // Numeric factorisation of K(E, D); E (m), D (n) are device vectors.
     void factor(const double* dE, const double* dD, const PrePass* pre = nullptr);
     // In-place refined solve of  -E dy + A dx = fy,  A' dy + D dx = fx.
@@ -338,6 +344,8 @@ class KktDevice {
     // matrix
     DevBuf<int> dkA_, diA_, dkAt_, diAt_;
     DevBuf<double> dA_, dAt_;
+    DevBuf<int> dtmap_;            // dAt_[d] = dA_[dtmap_[d]] (value_maps.h csr_value_map)
+    DevBuf<int> dqdiagmap_;        // dQdiag_[j] = dQ_[dqdiagmap_[j]], 0 where -1 (q_diag_map)
     // Q block (qnz_ > 0): CSC, its assembly map, its diagonal by y-node (old order)
     int qnz_ = 0, qmax_ = 1;
     DevBuf<int> dkQ_, diQ_;

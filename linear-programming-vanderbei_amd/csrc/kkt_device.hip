@@ -33,6 +33,7 @@
 #include "kkt_device.h"
 #include "kkt_kernels.h"
 #include "lp_io.h"
+#include "value_maps.h"
 
 namespace ipo {
 
@@ -950,6 +951,12 @@ void KktDevice::upload_plan(const int* kA, const int* iA, const double* A, const
     dkAt_.upload(kat, s);
     diAt_.upload(iat, s);
     dAt_.upload(at, s);
+    {
+        // where each entry of at came from (refresh_values): a local, synchronised here
+        const std::vector<int> tmap = csr_value_map(m, n, kA, iA);
+        dtmap_.upload(tmap, s);
+        IPO_HIP_CHECK(hipStreamSynchronize(s));
+    }
 
     dcol0_.upload(plan_.col0, s);
     drowptr_.upload(plan_.rowptr, s);
@@ -970,6 +977,8 @@ void KktDevice::upload_plan(const int* kA, const int* iA, const double* A, const
             for (int k = qb->kQ[j]; k < qb->kQ[j + 1]; k++)
                 if (qb->iQ[k] == j) qd[j] = qb->Q[k];
         dQdiag_.upload(qd, s);
+        const std::vector<int> qdm = q_diag_map(m, qb->kQ, qb->iQ);
+        dqdiagmap_.upload(qdm, s);
         // the long columns (kkt_device.h q_long_count), maybe none
         const std::vector<int> ql = q_long_columns(m, qb->kQ, knobs_.q_long);
         q_long_n_ = static_cast<int>(ql.size());
@@ -992,6 +1001,27 @@ void KktDevice::upload_plan(const int* kA, const int* iA, const double* A, const
     dupd_r1_.upload(plan_.upd_r1, s);
     drel_.upload(plan_.rel, s);
     dlevel_sups_.upload(plan_.level_sups, s);
+}
+
+// New values on the same pattern (ipo_hip_ctx_update): dA in
+// the constructor's CSC order and dQ in its kQ / iQ order, device arrays the
+// caller has validated, either null for "unchanged".  Copies them over dA_ /
+// dQ_ and regathers the CSR values and Q's diagonal through the maps built at
+// construction; factor() scatters dA_ / dQ_ anew on every call.  Drops a
+// pending pre-pass, resets nothing else.  Enqueued on the object's stream.
+void KktDevice::refresh_values(const double* dA, const double* dQ) {
+    hipStream_t s = stream_;
+    const int nz = static_cast<int>(dtmap_.size());
+    if (dA && nz > 0) {
+        IPO_HIP_CHECK(hipMemcpyAsync(dA_.get(), dA, nz * sizeof(double), hipMemcpyDeviceToDevice, s));
+        launch_gather_map(nz, dtmap_.get(), dA, dAt_.get(), s);
+    }
+    if (dQ) {
+        if (qnz_ <= 0) throw std::invalid_argument("kkt: new Q values for a factor without a Q block");
+        IPO_HIP_CHECK(hipMemcpyAsync(dQ_.get(), dQ, qnz_ * sizeof(double), hipMemcpyDeviceToDevice, s));
+        launch_gather_map(m_, dqdiagmap_.get(), dQ, dQdiag_.get(), s);
+    }
+    drop_prepass();
 }
 
 // Fused panel units and small panels per level (kkt_schedule.h)

@@ -23,12 +23,15 @@ class RowAxPlan {
   public:
     void build(int m, int n, const int* kA, const int* iA, const double* A, int npass, hipStream_t st);
     void launch(const double* x, double* ax, hipStream_t st) const;
+    // new values on the same pattern: dA (device) is A in build()'s CSC order
+    void refresh(const double* dA, hipStream_t st);
     int passes() const { return np_; }
 
   private:
-    int m_ = 0, np_ = 0;
+    int m_ = 0, np_ = 0, nz_ = 0;
     std::vector<int> rows_, nd_, dbase_;        // per pass: rows launched, diagonals, offset into dptr / dlen
     DevBuf<int> perm_, dptr_, dlen_, cols_;
+    DevBuf<int> src_;                           // per slice position: its CSC entry (value_maps.h row_ax_layout)
     DevBuf<double> vals_;
 };
 

@@ -84,6 +84,8 @@ EXPORTED = [
     "ipo_hip_symbolic_tail", "ipo_hip_kkt_schedule",
     "ipo_hip_solve_qp", "ipo_hip_solve_qp_ex", "ipo_hip_ctx_create_qp", "ipo_hip_mps_load_qp",
     "ipo_hip_q_times", "ipo_hip_kkt_q_long", "ipo_hip_ctx_q_long",
+    "ipo_hip_ctx_update", "ipo_hip_ctx_update_seconds", "ipo_hip_ctx_set_start", "ipo_hip_ctx_start_from_last",
+    "ipo_hip_value_maps",
 ]
 
 # int (*)(void *user, double *buf, long n, int op)  -- ipo_hip_allreduce_fn
@@ -176,6 +178,16 @@ def lib() -> C.CDLL:
     L.ipo_hip_ctx_destroy.restype = None
     L.ipo_hip_ctx_setup_seconds.argtypes = [_P]
     L.ipo_hip_ctx_setup_seconds.restype = _D
+    L.ipo_hip_ctx_update.argtypes = [_P, _P, _P, _P, _P, _P]
+    L.ipo_hip_ctx_update.restype = _I
+    L.ipo_hip_ctx_update_seconds.argtypes = [_P, C.POINTER(_D), C.POINTER(_D)]
+    L.ipo_hip_ctx_update_seconds.restype = None
+    L.ipo_hip_ctx_set_start.argtypes = [_P, _P, _P, _P, _P]
+    L.ipo_hip_ctx_set_start.restype = _I
+    L.ipo_hip_ctx_start_from_last.argtypes = [_P, _D]
+    L.ipo_hip_ctx_start_from_last.restype = _I
+    L.ipo_hip_value_maps.argtypes = [_I, _I, _P, _P, C.c_char_p, _P, C.c_long]
+    L.ipo_hip_value_maps.restype = C.c_long
     L.ipo_hip_dot_ordered.argtypes = [_P, _P, _I, _P]
     L.ipo_hip_dot_ordered.restype = _I
     L.ipo_hip_q_times.argtypes = [_I, _P, _P, _P, _P, _I, _P]
@@ -547,6 +559,58 @@ class Context:
         """Columns of Q summed by one wave each (IPO_HIP_Q_LONG); 0 without Q."""
         return lib().ipo_hip_ctx_q_long(self.h)
 
+    def _vec(self, a, size, what):
+        a = np.ascontiguousarray(a, np.float64)
+        if a.shape != (size,):
+            raise IpoHipError(f"{what}: expected {size} entries, got shape {a.shape}")
+        return a
+
+    def update(self, A=None, b=None, c=None, f=None, q=None):
+        """New numbers on the same pattern (ipo_hip_ctx_update): each of A
+        (the creation's CSC order), b, c, f and q (Q's values in the
+        creation's kQ / iQ order) replaces the context's, None leaves it.
+        The next run() is bitwise a fresh Context's on the new numbers.
+        Raises IpoHipError on a refusal (a non-finite value, an asymmetric Q,
+        q on a context without Q, a sharded context); the context then still
+        holds its old numbers."""
+        p = self.p
+        qnz = int(p.q[0][-1]) if getattr(p, "q", None) is not None else 0
+        arrs = [None if A is None else self._vec(A, p.nz, "update: A"),
+                None if b is None else self._vec(b, p.m, "update: b"),
+                None if c is None else self._vec(c, p.n, "update: c"),
+                None if f is None else np.array([f], np.float64),
+                # (q for a context without Q goes to the C side as it is: the refusal is there)
+                None if q is None else self._vec(q, qnz, "update: q") if qnz else np.ascontiguousarray(q, np.float64)]
+        if arrs[4] is not None and arrs[4].size == 0:
+            arrs[4] = np.zeros(1, np.float64)       # never a zero-length buffer; the C side refuses it
+        if lib().ipo_hip_ctx_update(self.h, *[None if a is None else _ptr(a) for a in arrs]):
+            raise IpoHipError("ctx update: " + last_error())
+
+    def update_seconds(self):
+        """(upload with validation, device refresh) wall seconds of the last update()."""
+        u, r = C.c_double(0.0), C.c_double(0.0)
+        lib().ipo_hip_ctx_update_seconds(self.h, C.byref(u), C.byref(r))
+        return u.value, r.value
+
+    def set_start(self, x, y, w, z):
+        """Start intpt, qp and pc from (x, y, w, z), every entry finite and
+        > 0, until clear_start(); hsd and hsdls then return 7."""
+        v = [self._vec(x, self.p.n, "set_start: x"), self._vec(y, self.p.m, "set_start: y"),
+             self._vec(w, self.p.m, "set_start: w"), self._vec(z, self.p.n, "set_start: z")]
+        # (a zero-length vector still needs a non-null pointer: all four null clears)
+        v = [a if a.size else np.ones(1) for a in v]
+        if lib().ipo_hip_ctx_set_start(self.h, *[_ptr(a) for a in v]):
+            raise IpoHipError("ctx set_start: " + last_error())
+
+    def clear_start(self):
+        if lib().ipo_hip_ctx_set_start(self.h, None, None, None, None):
+            raise IpoHipError("ctx clear_start: " + last_error())
+
+    def start_from_last(self, floor: float):
+        """Start from the iterate the last run() left, each entry raised to at least floor > 0."""
+        if lib().ipo_hip_ctx_start_from_last(self.h, float(floor)):
+            raise IpoHipError("ctx start_from_last: " + last_error())
+
     def solution(self):
         x = np.zeros(self.p.n); z = np.zeros(self.p.n); y = np.zeros(self.p.m); w = np.zeros(self.p.m)
         lib().ipo_hip_ctx_download(self.h, _ptr(x), _ptr(y), _ptr(w), _ptr(z))
@@ -707,6 +771,25 @@ def kkt_schedule(m, n, kA, iA, names, cus=256, nforced=0):
     if pos != n_out:
         raise IpoHipError("kkt_schedule: the arrays do not add up to the returned length")
     return d
+
+
+def value_maps(m, n, kA, iA, name):
+    """Host-only: one of the index maps Context.update() refreshes values
+    through (ipo_hip_value_maps): "csr", "jds" (with "jds.cols", "jds.perm",
+    "jds.dptr", "jds.dlen", "jds.dims"; IPO_HIP_AX_BLOCKS from the
+    environment), or for Q's pattern (m = n) "qdiag" and "qt"."""
+    kA = np.ascontiguousarray(kA, np.int32)
+    iA = np.ascontiguousarray(iA, np.int32)
+    if iA.size == 0:
+        iA = np.zeros(1, np.int32)
+    f = lib().ipo_hip_value_maps
+    n_out = f(m, n, _ptr(kA), _ptr(iA), name.encode(), None, 0)
+    if n_out < 0:
+        raise IpoHipError(last_error())
+    out = np.zeros(max(n_out, 1), np.int32)
+    if f(m, n, _ptr(kA), _ptr(iA), name.encode(), _ptr(out), out.size) != n_out:
+        raise IpoHipError("value_maps: the length changed between two calls")
+    return out[:n_out].copy()
 
 
 # ----------------------------------------------------------------- synthetic LPs
