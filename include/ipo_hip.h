@@ -156,6 +156,37 @@ void ipo_hip_ctx_update_seconds(const ipo_hip_ctx *ctx, double *upload_s, double
 int ipo_hip_ctx_set_start(ipo_hip_ctx *ctx, const double *x, const double *y, const double *w, const double *z);
 int ipo_hip_ctx_start_from_last(ipo_hip_ctx *ctx, double floor);
 
+/* A start rule for the same methods (1, 3, 4), used where no point is held.
+ * IPO_HIP_START_MEHROTRA: Mehrotra's point, computed on the device on every
+ * run from the context's current numbers (so after ipo_hip_ctx_update from
+ * the new ones): with E = D = 1, one factorisation and two refined solves
+ * give the least-norm solutions of A x + w = b and A'y - z = c (with Q the
+ * first in the norm of I + Q); x, w are raised by max(0, -1.5 min(x, w)), y, z
+ * by max(0, -1.5 min(y, z)), then with g = x'z + w'y by g / (2 (sum z +
+ * sum y)) and g / (2 (sum x + sum w)) (both 1 when g or a sum is not > 0:
+ * b = 0 and c = 0).  The work counts in the run's t_solve_s, factors (+1) and
+ * solves (+2).  A run whose point has an entry not > 0 returns 7.
+ * IPO_HIP_START_DEFAULT: every variable 1000.  The default start detects
+ * infeasible and unbounded problems sooner: those tests depend on the
+ * scale of the start.
+ * The latest call wins: setting a rule clears a held point;
+ * ipo_hip_ctx_set_start (its clear call too) and ipo_hip_ctx_start_from_last
+ * put the rule back to the default.  Methods 0 and 2 return 7 with an error
+ * text and no iteration while the Mehrotra rule is set.  Returns 0, or -1 for
+ * an unknown rule or a sharded context.
+ * ipo_hip_ctx_start_point computes the point of `rule` from the context's
+ * current numbers into x, z (n), y, w (m) (any may be NULL) and changes
+ * nothing the next run sees: not the rule, a held start, the last iterate or
+ * eps_diag.  Rule 0 gives 1000 everywhere.  Returns 0, or -1.
+ * The one-shot entries (solver, ipo_hip_solve, ipo_hip_solve_qp[_ex],
+ * ipo_hip_run_mps[_ex]) read IPO_HIP_START=mehrotra|default from the
+ * environment when called: an unknown value returns 7 with an error text,
+ * and so does mehrotra with methods 0 and 2.  Contexts ignore the variable. */
+#define IPO_HIP_START_DEFAULT 0
+#define IPO_HIP_START_MEHROTRA 1
+int ipo_hip_ctx_set_start_rule(ipo_hip_ctx *ctx, int rule);
+int ipo_hip_ctx_start_point(ipo_hip_ctx *ctx, int rule, double *x, double *y, double *w, double *z);
+
 /* ---- quadratic programs (an extension: the reference has no QP loop) --------
  * Solves  max c'x + f - x'Qx / 2  s.t.  Ax <= b, x >= 0  by intpt.c's
  * primal-dual path following with Q carried through (method 3, "qp": the

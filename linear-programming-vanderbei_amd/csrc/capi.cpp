@@ -38,6 +38,15 @@ ipo::Method method_from_env() {
     return ipo::Method::Hsd;
 }
 
+// IPO_HIP_START, the one-shot entries' start rule (solve_impl): unset or
+// "default", "mehrotra"; anything else is refused
+ipo::StartRule start_rule_from_env() {
+    const char* e = std::getenv("IPO_HIP_START");
+    if (!e || !std::strcmp(e, "default")) return ipo::StartRule::Default;
+    if (!std::strcmp(e, "mehrotra")) return ipo::StartRule::Mehrotra;
+    throw std::invalid_argument(std::string("IPO_HIP_START=") + e + ": unknown start rule (default, mehrotra)");
+}
+
 ipo::Method method_from_int(int m) {
     return m == 1   ? ipo::Method::Intpt
            : m == 2 ? ipo::Method::Hsdls
@@ -125,8 +134,13 @@ int solve_impl(ipo::Method method, int m, int n, int nz, const int* iA, const in
     if (dev_err) *dev_err = false;
     try {
         if (q && q->kQ) validate_q(n, q->kQ, q->iQ, q->Q);
+        const ipo::StartRule rule = start_rule_from_env();
+        if (rule == ipo::StartRule::Mehrotra && (method == ipo::Method::Hsd || method == ipo::Method::Hsdls))
+            throw std::invalid_argument("IPO_HIP_START=mehrotra: hsd and hsdls take no start point (their state "
+                                        "includes phi and psi); run intpt, qp or pc");
         if (method != ipo::Method::Hsdls) print_small(trace, m, n, kA, iA, A, b, c);   // hsdls.c has no echo
         ipo::IpmSolver S(m, n, kA, iA, A, b, c, f, nullptr, nullptr, q);
+        if (rule != ipo::StartRule::Default) S.set_start_rule(rule);
         ipo::IpmOptions opt;
         opt.method = method;
         opt.trace = trace;
@@ -325,6 +339,31 @@ int ipo_hip_ctx_set_start(ipo_hip_ctx* ctx, const double* x, const double* y, co
 int ipo_hip_ctx_start_from_last(ipo_hip_ctx* ctx, double floor) {
     try {
         ctx->solver->start_from_last(floor);
+        return 0;
+    } catch (const std::exception& e) {
+        set_err(e.what());
+        return -1;
+    }
+}
+
+int ipo_hip_ctx_set_start_rule(ipo_hip_ctx* ctx, int rule) {
+    try {
+        if (rule != IPO_HIP_START_DEFAULT && rule != IPO_HIP_START_MEHROTRA)
+            throw std::invalid_argument("set_start_rule: unknown rule " + std::to_string(rule));
+        ctx->solver->set_start_rule(rule == IPO_HIP_START_MEHROTRA ? ipo::StartRule::Mehrotra : ipo::StartRule::Default);
+        return 0;
+    } catch (const std::exception& e) {
+        set_err(e.what());
+        return -1;
+    }
+}
+
+int ipo_hip_ctx_start_point(ipo_hip_ctx* ctx, int rule, double* x, double* y, double* w, double* z) {
+    try {
+        if (rule != IPO_HIP_START_DEFAULT && rule != IPO_HIP_START_MEHROTRA)
+            throw std::invalid_argument("start_point: unknown rule " + std::to_string(rule));
+        ctx->solver->start_point(rule == IPO_HIP_START_MEHROTRA ? ipo::StartRule::Mehrotra : ipo::StartRule::Default, x, y,
+                                 w, z);
         return 0;
     } catch (const std::exception& e) {
         set_err(e.what());

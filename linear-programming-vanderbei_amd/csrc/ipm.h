@@ -78,7 +78,18 @@ constexpr int kIsPhiNext = 14;  // [2] the next iteration's phi, psi (k_hsd_thet
 constexpr int kIsPcRatio = 16;  // the predictor's largest ratio t (k_pc_affine)
 constexpr int kIsPcDots = 17;   // [6] z'dxa, x'dza, w'dya, y'dwa, dxa'dza, dya'dwa (g1 and g2's terms)
 constexpr int kIsPcMu = 23;     // the centring mu k_pc_rhs and k_pc_directions read (k_pc_mu)
-constexpr int kIsCount = 24;
+// the Mehrotra start (IpmSolver::mehrotra_start; none of them is read back):
+constexpr int kIsMsNegMin = 24; // [2] -min(x~, w~), -min(y~, z~) of the least-squares point (k_ms_unpack)
+constexpr int kIsMsDelta = 26;  // [2] the shifts delta_p, delta_d (k_ms_delta)
+constexpr int kIsMsSums = 28;   // [3] g = x'z + w'y, Sp = sum x + sum w, Sd = sum z + sum y (k_ms_shift)
+constexpr int kIsMsEps = 31;    // [2] the balancing shifts eps_p, eps_d (k_ms_eps)
+constexpr int kIsCount = 33;
+
+// How a run of Intpt, Qp or Pc chooses its line 0 when no point is held:
+// every variable 1000, or Mehrotra's least-squares point shifted into the
+// interior and balanced, computed on the device from the
+// problem's current numbers.
+enum class StartRule { Default = 0, Mehrotra = 1 };
 
 // Problem uploaded to HBM once; run() iterates from the reference's start
 // point and can be called repeatedly (the bench times run()).
@@ -128,6 +139,18 @@ class IpmSolver {
     // floor > 0 (one kernel, no host round trip).  Throws before any run().
     void start_from_last(double floor);
     bool has_start() const { return has_start_; }
+    // The rule for line 0 of Intpt, Qp and Pc.  The latest
+    // call wins: setting a rule clears a held point, and set_start (its clear
+    // call too) and start_from_last put the rule back to Default.  Under
+    // Mehrotra every run() computes its start from the numbers then current
+    // (one factorisation and two refined solves, counted in the run's time
+    // and statistics); Hsd and Hsdls refuse to run.  Throws on a sharded solver.
+    void set_start_rule(StartRule r);
+    StartRule start_rule() const { return rule_; }
+    // The rule's point for the current numbers into host vectors x, z (n), y,
+    // w (m); Default: 1000 everywhere.  Changes nothing a later run() sees:
+    // not the rule, a held start, the last iterate or the factor's eps_diag.
+    void start_point(StartRule r, double* x, double* y, double* w, double* z);
 
   private:
     int run_hsd(const IpmOptions& opt, IpmResult* res);
@@ -154,8 +177,15 @@ class IpmSolver {
     DevBuf<double> ax_;
     RowAxPlan axplan_;
     void print_dims(FILE* tr) const;
-    // x, z, y, w of a path-following run's line 0: the held start, or v everywhere
-    void init_point(double v);
+    // x, z, y, w of a path-following run's line 0: the held start, the
+    // rule's point, or v everywhere
+    void init_point(double v, IpmResult* res);
+    // Mehrotra's start into device vectors x, z (n), y, w (m); returns the
+    // refinement passes of its two solves.  Leaves the factor of E = D = 1
+    // behind and whatever eps_diag that factorisation grew to: the caller
+    // puts eps_diag back.  Uses D_, E_, gx_, gy_, dx_, dy_, part_ and the
+    // kIsMs slots.  Throws std::runtime_error if an entry came out not > 0.
+    long mehrotra_start(double* x, double* y, double* w, double* z);
     void alloc_start();
     // the value maps of update() (value_maps.h), uploaded at construction
     int nz_ = 0, qnz_ = 0;
@@ -167,6 +197,7 @@ class IpmSolver {
     double t_upd_upload_ = 0.0, t_upd_refresh_ = 0.0;
     // the start point: held (sx_ ...) and set_start()'s staging (tx_ ...)
     bool has_start_ = false, ran_ = false;
+    StartRule rule_ = StartRule::Default;
     DevBuf<double> sx_, sy_, sw_, sz_, tx_, ty_, tw_, tz_;
 
     int m_, n_;

@@ -11,6 +11,7 @@
 // allreduced before it is read.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -503,6 +504,109 @@ __global__ void k_pc_theta(double* sc) {
     sc[kIsTheta] = (t == 0.0 || 0.95 / t > 1.0) ? 1.0 : 0.95 / t;
 }
 
+// ---------------------------------------------------------------- the Mehrotra start
+// IpmSolver::mehrotra_start, SW as above.  The factor's
+// D = E = 1 and the two systems' right-hand sides, (fy, fx) = (b, 0) into
+// (by, bx) and (0, c) into (cy, cx), the x block's negated when SW.
+template <bool SW>
+__global__ void __launch_bounds__(NT)
+k_ms_fill(int m, int n, const double* __restrict__ b, const double* __restrict__ c, double* __restrict__ D,
+          double* __restrict__ E, double* __restrict__ bx, double* __restrict__ by, double* __restrict__ cx,
+          double* __restrict__ cy) {
+    for (int i = blockIdx.x * NT + threadIdx.x; i < m + n; i += kRedBlocks * NT) {
+        if (i < n) {
+            D[i] = 1.0;
+            bx[i] = 0.0;
+            cx[i] = SW ? -c[i] : c[i];
+        } else {
+            const int j = i - n;
+            E[j] = 1.0;
+            by[j] = b[j];
+            cy[j] = 0.0;
+        }
+    }
+}
+
+// The two solutions unpacked: x~ = dx, w~ = -dy of the first system, y~ = dy,
+// z~ = -dx of the second (the swapped solve leaves -dy where the LP's leaves
+// dy).  part: kRedBlocks partials each of max(-x~, -w~) and max(-y~, -z~),
+// the two minima negated so the common max finisher applies.
+template <bool SW>
+__global__ void __launch_bounds__(NT)
+k_ms_unpack(int m, int n, const double* __restrict__ bx, const double* __restrict__ by, const double* __restrict__ cx,
+            const double* __restrict__ cy, double* __restrict__ x, double* __restrict__ w, double* __restrict__ y,
+            double* __restrict__ z, double* __restrict__ part) {
+    __shared__ double sh[4];
+    double np = -HUGE_VAL, nd = -HUGE_VAL;
+    for (int i = blockIdx.x * NT + threadIdx.x; i < m + n; i += kRedBlocks * NT) {
+        if (i < n) {
+            const double xv = bx[i], zv = -cx[i];
+            x[i] = xv; z[i] = zv;
+            np = fmax(np, -xv);
+            nd = fmax(nd, -zv);
+        } else {
+            const int j = i - n;
+            const double wv = SW ? by[j] : -by[j], yv = SW ? -cy[j] : cy[j];
+            w[j] = wv; y[j] = yv;
+            np = fmax(np, -wv);
+            nd = fmax(nd, -yv);
+        }
+    }
+    np = block_max(np, sh);
+    nd = block_max(nd, sh);
+    if (threadIdx.x == 0) { part[blockIdx.x] = np; part[kRedBlocks + blockIdx.x] = nd; }
+}
+
+// delta_p = max(0, -1.5 min(x~, w~)), delta_d = max(0, -1.5 min(y~, z~));
+// reads kIsMsNegMin, writes kIsMsDelta
+__global__ void k_ms_delta(double* sc) {
+    sc[kIsMsDelta] = fmax(0.0, 1.5 * sc[kIsMsNegMin]);
+    sc[kIsMsDelta + 1] = fmax(0.0, 1.5 * sc[kIsMsNegMin + 1]);
+}
+
+// x, w += sh[0], y, z += sh[1].  With part: the shift by kIsMsDelta, and
+// kRedBlocks partials each of g = x'z + w'y, Sp = sum x + sum w and Sd =
+// sum z + sum y of the shifted point: a thread's entries in index order, the
+// block's by block_sum's tree, so the sums have the same bits on every run.
+// Without: the shift by kIsMsEps.
+__global__ void __launch_bounds__(NT)
+k_ms_shift(int m, int n, const double* __restrict__ sh2, double* __restrict__ x, double* __restrict__ w,
+           double* __restrict__ y, double* __restrict__ z, double* __restrict__ part) {
+    __shared__ double sh[4];
+    const double sp = sh2[0], sd = sh2[1];
+    double g = 0.0, Sp = 0.0, Sd = 0.0;
+    for (int i = blockIdx.x * NT + threadIdx.x; i < m + n; i += kRedBlocks * NT) {
+        if (i < n) {
+            const double xv = x[i] + sp, zv = z[i] + sd;
+            x[i] = xv; z[i] = zv;
+            g += xv * zv; Sp += xv; Sd += zv;
+        } else {
+            const int j = i - n;
+            const double wv = w[j] + sp, yv = y[j] + sd;
+            w[j] = wv; y[j] = yv;
+            g += wv * yv; Sp += wv; Sd += yv;
+        }
+    }
+    if (!part) return;
+    g = block_sum(g, sh);
+    Sp = block_sum(Sp, sh);
+    Sd = block_sum(Sd, sh);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = g;
+        part[kRedBlocks + blockIdx.x] = Sp;
+        part[2 * kRedBlocks + blockIdx.x] = Sd;
+    }
+}
+
+// eps_p = g / (2 Sd), eps_d = g / (2 Sp) if g, Sp and Sd are all > 0, else
+// both 1 (b = 0 and c = 0); reads kIsMsSums, writes kIsMsEps
+__global__ void k_ms_eps(double* sc) {
+    const double g = sc[kIsMsSums], Sp = sc[kIsMsSums + 1], Sd = sc[kIsMsSums + 2];
+    const bool ok = g > 0.0 && Sp > 0.0 && Sd > 0.0;
+    sc[kIsMsEps] = ok ? g / (2.0 * Sd) : 1.0;
+    sc[kIsMsEps + 1] = ok ? g / (2.0 * Sp) : 1.0;
+}
+
 // host copy of ls_step for the (phi, psi) pair (hsdls.c:229)
 double ls_step_host(double xj, double zj, double dxj, double dzj, double beta, double delta, double mu) {
     const double a = dxj * dzj;
@@ -667,6 +771,9 @@ int IpmSolver::run(const IpmOptions& opt, IpmResult* res) {
     if (has_start_ && !qp && !pc && opt.method != Method::Intpt)
         throw std::invalid_argument("a start point is set: hsd and hsdls take none (their state includes phi and psi); "
                                     "clear it, or run intpt, qp or pc");
+    if (rule_ == StartRule::Mehrotra && !qp && !pc && opt.method != Method::Intpt)
+        throw std::invalid_argument("the start rule mehrotra is set: hsd and hsdls take no start point (their state "
+                                    "includes phi and psi); set the default rule, or run intpt, qp or pc");
     KktDevice& K = *kkt_;
     res->t_setup_s = t_setup_;
     K.enable_timing(opt.timing);
@@ -686,7 +793,7 @@ int IpmSolver::run(const IpmOptions& opt, IpmResult* res) {
     return st;
 }
 
-void IpmSolver::init_point(double v) {
+void IpmSolver::init_point(double v, IpmResult* res) {
     hipStream_t s = stream_;
     const int m = m_, n = n_;
     if (has_start_) {
@@ -695,6 +802,14 @@ void IpmSolver::init_point(double v) {
             const size_t len = (c.first == &x_ || c.first == &z_) ? n : m;
             if (len) IPO_HIP_CHECK(hipMemcpyAsync(c.first->get(), c.second->get(), len * sizeof(double), hipMemcpyDeviceToDevice, s));
         }
+        return;
+    }
+    if (rule_ == StartRule::Mehrotra) {
+        res->refine_passes += mehrotra_start(x_.get(), y_.get(), w_.get(), z_.get());
+        // the iteration finds the factor as after a held start: run()'s
+        // eps_diag, whatever the start's factorisation grew it to (that
+        // factorisation asked for no pre-pass, so none is pending)
+        kkt_->set_epsdiag(1.0e-14);
         return;
     }
     for (DevBuf<double>* p : {&x_, &z_}) hipLaunchKernelGGL(k_fill, dim3(ceil_div(n, NT)), dim3(NT), 0, s, n, v, p->get());
@@ -706,6 +821,108 @@ namespace {
 constexpr int kVfA = 0, kVfB = 1, kVfC = 2, kVfQ = 3, kVfQsym = 4, kVfX = 5, kVfY = 6, kVfW = 7, kVfZ = 8, kVfCount = 9;
 constexpr int kVfNone = 0x7f7f7f7f;      // a slot no kernel lowered (memset 0x7f)
 }  // namespace
+
+// Mehrotra's start point.  "Solve" is the factor's refined
+// solve [-E A; A' D (+ Q)] (dy, dx) = (fy, fx), the LP's own factor or, for
+// a solver with Q, the swapped one in run_qp's calling convention.
+//   1. E = 1, D = 1, one factorisation
+//   2. (fy, fx) = (b, 0): x~ = dx, w~ = -dy, so A x~ + w~ = b at least norm
+//      (with Q the norm weighted by I + Q)
+//   3. (fy, fx) = (0, c) with the same factor: y~ = dy, z~ = -dx, for an LP
+//      A'y~ - z~ = c at least norm
+//   4. delta_p = max(0, -1.5 min(x~, w~)) onto x~, w~; delta_d = max(0, -1.5
+//      min(y~, z~)) onto y~, z~
+//   5. g = x'z + w'y, Sp = sum x + sum w, Sd = sum z + sum y; eps_p =
+//      g / (2 Sd) onto x, w and eps_d = g / (2 Sp) onto y, z; both 1 unless
+//      g, Sp and Sd are all > 0
+// The scalars stay on the device (the kIsMs slots); the one read-back is the
+// check that every entry came out finite and > 0.
+long IpmSolver::mehrotra_start(double* x, double* y, double* w, double* z) {
+    hipStream_t s = stream_;
+    const int m = m_, n = n_;
+    KktDevice& K = *kkt_;
+    double* sc = scal_.get();
+    long passes = 0;
+    const auto go = [&](auto fill, auto unpack) {
+        hipLaunchKernelGGL(fill, dim3(kRedBlocks), dim3(NT), 0, s, m, n, b_.get(), c_.get(), D_.get(), E_.get(), gx_.get(),
+                           gy_.get(), dx_.get(), dy_.get());
+        if (has_q_) {
+            K.factor(D_.get(), E_.get());
+            K.solve(D_.get(), E_.get(), gx_.get(), gy_.get());
+            passes += K.last_passes();
+            K.solve(D_.get(), E_.get(), dx_.get(), dy_.get());
+        } else {
+            K.factor(E_.get(), D_.get());
+            K.solve(E_.get(), D_.get(), gy_.get(), gx_.get());
+            passes += K.last_passes();
+            K.solve(E_.get(), D_.get(), dy_.get(), dx_.get());
+        }
+        passes += K.last_passes();
+        hipLaunchKernelGGL(unpack, dim3(kRedBlocks), dim3(NT), 0, s, m, n, gx_.get(), gy_.get(), dx_.get(), dy_.get(), x, w,
+                           y, z, part_.get());
+    };
+    if (has_q_) go(k_ms_fill<true>, k_ms_unpack<true>);
+    else go(k_ms_fill<false>, k_ms_unpack<false>);
+    hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 2, 3u, sc + kIsMsNegMin);
+    hipLaunchKernelGGL(k_ms_delta, dim3(1), dim3(1), 0, s, sc);
+    hipLaunchKernelGGL(k_ms_shift, dim3(kRedBlocks), dim3(NT), 0, s, m, n, static_cast<const double*>(sc + kIsMsDelta), x,
+                       w, y, z, part_.get());
+    hipLaunchKernelGGL(k_finish_reduce, dim3(1), dim3(kRedThreads), 0, s, part_.get(), 3, 0u, sc + kIsMsSums);
+    hipLaunchKernelGGL(k_ms_eps, dim3(1), dim3(1), 0, s, sc);
+    hipLaunchKernelGGL(k_ms_shift, dim3(kRedBlocks), dim3(NT), 0, s, m, n, static_cast<const double*>(sc + kIsMsEps), x, w,
+                       y, z, static_cast<double*>(nullptr));
+    if (vfirst_.size() == 0) vfirst_.alloc(kVfCount);
+    IPO_HIP_CHECK(hipMemsetAsync(vfirst_.get(), 0x7f, kVfCount * sizeof(int), s));
+    int* vf = vfirst_.get();
+    launch_first_nonpositive(n, x, vf + kVfX, s);
+    launch_first_nonpositive(m, y, vf + kVfY, s);
+    launch_first_nonpositive(m, w, vf + kVfW, s);
+    launch_first_nonpositive(n, z, vf + kVfZ, s);
+    int first[kVfCount];
+    IPO_HIP_CHECK(hipMemcpyAsync(first, vf, sizeof first, hipMemcpyDeviceToHost, s));
+    IPO_HIP_CHECK(hipStreamSynchronize(s));
+    const std::pair<int, const char*> chk[] = {{kVfX, "x"}, {kVfY, "y"}, {kVfW, "w"}, {kVfZ, "z"}};
+    for (const auto& c : chk)
+        if (first[c.first] != kVfNone && first[c.first] < ((c.first == kVfX || c.first == kVfZ) ? n : m))
+            throw std::runtime_error(std::string("start rule mehrotra: ") + c.second + "[" + std::to_string(first[c.first]) +
+                                     "] of the start point is not a finite value > 0");
+    return passes;
+}
+
+void IpmSolver::set_start_rule(StartRule r) {
+    if (sharded_) throw std::invalid_argument("set_start_rule: not supported on a sharded solver");
+    rule_ = r;
+    has_start_ = false;
+}
+
+void IpmSolver::start_point(StartRule r, double* x, double* y, double* w, double* z) {
+    if (sharded_) throw std::invalid_argument("start_point: not supported on a sharded solver");
+    if (r == StartRule::Default) {
+        if (x) std::fill(x, x + n_, 1000.0);
+        if (z) std::fill(z, z + n_, 1000.0);
+        if (y) std::fill(y, y + m_, 1000.0);
+        if (w) std::fill(w, w + m_, 1000.0);
+        return;
+    }
+    alloc_start();
+    // into set_start()'s staging, the factor's host-side state (eps_diag,
+    // counters) put back afterwards: x_ ... and a held start stay as they are
+    KktDevice& K = *kkt_;
+    const KktDevice::HostState hs = K.host_state();
+    K.set_epsdiag(1.0e-14);
+    try {
+        mehrotra_start(tx_.get(), ty_.get(), tw_.get(), tz_.get());
+    } catch (...) {
+        K.restore_host_state(hs);
+        throw;
+    }
+    K.restore_host_state(hs);
+    if (x) tx_.download(x, n_, stream_);
+    if (y) ty_.download(y, m_, stream_);
+    if (w) tw_.download(w, m_, stream_);
+    if (z) tz_.download(z, n_, stream_);
+    IPO_HIP_CHECK(hipStreamSynchronize(stream_));
+}
 
 void IpmSolver::update(const double* A, const double* b, const double* c, const double* f, const double* Q) {
     if (sharded_)
@@ -773,7 +990,7 @@ void IpmSolver::alloc_start() {
 
 void IpmSolver::set_start(const double* x, const double* y, const double* w, const double* z) {
     if (sharded_) throw std::invalid_argument("set_start: not supported on a sharded solver");
-    if (!x && !y && !w && !z) { has_start_ = false; return; }
+    if (!x && !y && !w && !z) { has_start_ = false; rule_ = StartRule::Default; return; }
     if (!x || !y || !w || !z) throw std::invalid_argument("set_start: x, y, w and z are given together (all null clears the start)");
     hipStream_t s = stream_;
     const int m = m_, n = n_;
@@ -801,6 +1018,7 @@ void IpmSolver::set_start(const double* x, const double* y, const double* w, con
     launch_clamp_copy4(J, 0.0, s);
     IPO_HIP_CHECK(hipStreamSynchronize(s));
     has_start_ = true;
+    rule_ = StartRule::Default;
 }
 
 void IpmSolver::start_from_last(double floor) {
@@ -815,6 +1033,7 @@ void IpmSolver::start_from_last(double floor) {
     J.src[3] = z_.get(); J.dst[3] = sz_.get(); J.len[3] = n_;
     launch_clamp_copy4(J, floor, stream_);
     has_start_ = true;
+    rule_ = StartRule::Default;
 }
 
 int IpmSolver::run_hsd(const IpmOptions& opt, IpmResult* res) {
@@ -1088,7 +1307,7 @@ int IpmSolver::run_intpt(const IpmOptions& opt, IpmResult* res) {
     hipStream_t s = stream_;
     const int gv = ceil_div(m + n, NT);
     FILE* tr = opt.trace;
-    init_point(1000.0);
+    init_point(1000.0, res);
     const double delta = 0.02, r = 0.9;
     double normr0 = HUGE_VAL, norms0 = HUGE_VAL;
     if (tr) {
@@ -1171,7 +1390,7 @@ int IpmSolver::run_qp(const IpmOptions& opt, IpmResult* res) {
     hipStream_t s = stream_;
     const int gv = ceil_div(m + n, NT);
     FILE* tr = opt.trace;
-    init_point(1000.0);
+    init_point(1000.0, res);
     const double delta = 0.02, r = 0.9;
     double normr0 = HUGE_VAL, norms0 = HUGE_VAL;
     if (tr) {
@@ -1262,7 +1481,7 @@ int IpmSolver::run_pc(const IpmOptions& opt, IpmResult* res) {
     hipStream_t s = stream_;
     const int gv = ceil_div(m + n, NT);
     FILE* tr = opt.trace;
-    init_point(1000.0);
+    init_point(1000.0, res);
     double normr0 = HUGE_VAL, norms0 = HUGE_VAL, normr1 = 0.0, norms1 = 0.0;
     if (tr) {
         print_dims(tr);

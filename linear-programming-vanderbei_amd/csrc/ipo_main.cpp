@@ -1,13 +1,16 @@
-// ipo_main.cpp -- `ipo_hip file.mps [hsd|intpt|hsdls|qp|pc] [--free=split] [--no-out]`:
+// ipo_main.cpp -- `ipo_hip file.mps [hsd|intpt|hsdls|qp|pc] [mehrotra|default] [--free=split] [--no-out]`:
 // the reference's ipo driver (src/common/main.c:16-58) on top of
 // libipo_hip.so; same stdout, and like main.c:54-56 the solution report
 // <NAME>.out (iolp.c:976-1045) in the working directory unless --no-out.
 // --free=split: the free-variable extension (include/ipo_hip.h).  qp: the
 // file's quadratic program, QUADS included (an extension; the LP methods
 // ignore QUADS as the reference does).  pc: the predictor-corrector
-// extension on the same problem, a file without QUADS being the LP.  Extra
+// extension on the same problem, a file without QUADS being the LP.
+// mehrotra / default: the start rule of intpt, qp and pc (IPO_HIP_START, which
+// the word overrides).  Extra
 // timing goes to stderr so stdout can be diffed against .sol traces.
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -15,7 +18,7 @@
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s file.mps [hsd|intpt|hsdls|qp|pc] [--free=split] [--no-out]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s file.mps [hsd|intpt|hsdls|qp|pc] [mehrotra|default] [--free=split] [--no-out]\n", argv[0]);
         return 1;
     }
     int method = 0, flags = 0;
@@ -25,6 +28,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "hsdls")) method = 2;
         else if (!std::strcmp(argv[a], "qp")) method = 3;
         else if (!std::strcmp(argv[a], "pc")) method = 4;
+        else if (!std::strcmp(argv[a], "mehrotra") || !std::strcmp(argv[a], "default")) setenv("IPO_HIP_START", argv[a], 1);
         else if (!std::strcmp(argv[a], "--free=split")) flags |= IPO_HIP_SPLIT_FREE;
         else if (!std::strcmp(argv[a], "--no-out")) out = false;
     }

@@ -31,6 +31,7 @@ STATUS_TEXT = {
 }
 METHODS = {"hsd": 0, "intpt": 1, "hsdls": 2, "qp": 3, "pc": 4}
 Q_METHODS = ("qp", "pc")      # the methods that take a problem with q
+START_RULES = {"default": 0, "mehrotra": 1}      # include/ipo_hip.h IPO_HIP_START_*
 
 
 class IpoHipError(RuntimeError):
@@ -85,7 +86,7 @@ EXPORTED = [
     "ipo_hip_solve_qp", "ipo_hip_solve_qp_ex", "ipo_hip_ctx_create_qp", "ipo_hip_mps_load_qp",
     "ipo_hip_q_times", "ipo_hip_kkt_q_long", "ipo_hip_ctx_q_long",
     "ipo_hip_ctx_update", "ipo_hip_ctx_update_seconds", "ipo_hip_ctx_set_start", "ipo_hip_ctx_start_from_last",
-    "ipo_hip_value_maps",
+    "ipo_hip_value_maps", "ipo_hip_ctx_set_start_rule", "ipo_hip_ctx_start_point",
 ]
 
 # int (*)(void *user, double *buf, long n, int op)  -- ipo_hip_allreduce_fn
@@ -186,6 +187,10 @@ def lib() -> C.CDLL:
     L.ipo_hip_ctx_set_start.restype = _I
     L.ipo_hip_ctx_start_from_last.argtypes = [_P, _D]
     L.ipo_hip_ctx_start_from_last.restype = _I
+    L.ipo_hip_ctx_set_start_rule.argtypes = [_P, _I]
+    L.ipo_hip_ctx_set_start_rule.restype = _I
+    L.ipo_hip_ctx_start_point.argtypes = [_P, _I, _P, _P, _P, _P]
+    L.ipo_hip_ctx_start_point.restype = _I
     L.ipo_hip_value_maps.argtypes = [_I, _I, _P, _P, C.c_char_p, _P, C.c_long]
     L.ipo_hip_value_maps.restype = C.c_long
     L.ipo_hip_dot_ordered.argtypes = [_P, _P, _I, _P]
@@ -610,6 +615,25 @@ class Context:
         """Start from the iterate the last run() left, each entry raised to at least floor > 0."""
         if lib().ipo_hip_ctx_start_from_last(self.h, float(floor)):
             raise IpoHipError("ctx start_from_last: " + last_error())
+
+    def set_start_rule(self, rule: str):
+        """The start of intpt, qp and pc where no point is held: "default"
+        (every variable 1000) or "mehrotra" (computed on the device on every
+        run from the context's current numbers; hsd and hsdls then return 7).
+        The latest of set_start_rule, set_start, clear_start and
+        start_from_last wins.  Raises IpoHipError for an unknown rule or a
+        sharded context."""
+        if lib().ipo_hip_ctx_set_start_rule(self.h, START_RULES.get(rule, -1)):
+            raise IpoHipError("ctx set_start_rule: " + last_error())
+
+    def start_point(self, rule: str = "mehrotra"):
+        """(x, y, w, z) of the rule's start for the context's current numbers;
+        changes nothing the next run() sees."""
+        x = np.zeros(max(self.p.n, 1)); z = np.zeros(max(self.p.n, 1))
+        y = np.zeros(max(self.p.m, 1)); w = np.zeros(max(self.p.m, 1))
+        if lib().ipo_hip_ctx_start_point(self.h, START_RULES.get(rule, -1), _ptr(x), _ptr(y), _ptr(w), _ptr(z)):
+            raise IpoHipError("ctx start_point: " + last_error())
+        return x[:self.p.n], y[:self.p.m], w[:self.p.m], z[:self.p.n]
 
     def solution(self):
         x = np.zeros(self.p.n); z = np.zeros(self.p.n); y = np.zeros(self.p.m); w = np.zeros(self.p.m)
